@@ -13,7 +13,7 @@ with its predictor tables), actions already resident in HBM.  Episodes (286 step
 is inside the timed region.  Kernel durations come from HIP events the library
 records around every --time-every-th launch, on the launch's stream.
 
-Launch:  python bench.py [--gpus N --steps K --warmup W]
+Launch:  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
          N>1: under torch.distributed.run (one rank per GPU, WORLD_SIZE must
          equal N), or started directly, in which case bench.py runs
          torch.distributed.run --nproc-per-node N as a child process before
@@ -21,10 +21,19 @@ Launch:  python bench.py [--gpus N --steps K --warmup W]
          Weak scaling, no collective on the step path; barrier +
          max-over-ranks timing.
 
-The CPU baseline (N=1 only) runs first, before the GPU is touched: the oracle
-on 1 process and on 8 forked processes; the reference's own loop cannot run on
-the GPU host, so its figures (tools/ref_cpu_loop.py, build container) are
-copied in from profiles/ref_cpu_loop.json as a labelled row.
+A plain run does what the headline needs and no more: it builds the env and the
+action pool, runs the cold first episode (the power flow's tables and every
+step's launch state are built there, once), warms up, times the K steps, writes
+the last timed step's outputs if --dump-outputs is given, and prints the line.
+Everything else is behind --full: the CPU baseline, the measured copy ceiling,
+the kernel-timing pass with the roofline figures, the whole-episode pass with
+its gathered statistics, and the variants (hipGraph, fp32 storage, the other
+power-flow rule, the rule without its table).
+
+--full: the CPU baseline (N=1 only) runs first, before the GPU is touched: the
+oracle on 1 process and on 8 forked processes; the reference's own loop's
+figures (tools/ref_cpu_loop.py) are copied in from profiles/ref_cpu_loop.json
+as a labelled row.
 """
 import argparse
 import gc
@@ -44,6 +53,7 @@ sys.path.insert(0, REPO)
 N_AGENTS = 5
 ACT_DIM = 8
 BATCH_PER_GPU = 65536
+DUMP_MAX_BYTES = 60 * 10 ** 6  # --dump-outputs writes at most this much (the default batch: 47.7 MB)
 HBM_PEAK_GBS = 8000.0        # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.3 measured achievable)
 FP64_PEAK_TFS = 78.6         # MI355X spec, FP64 vector (= FP64 matrix); tools/micro MFMA probe 68.7
 # k_coord_agents_std -- algorithmic HBM bytes per (env, agent), fp64 env-minor SoA:
@@ -137,6 +147,15 @@ def parse():
     ap.add_argument("--batch", type=int, default=BATCH_PER_GPU)
     ap.add_argument("--action-pool", type=int, default=64,
                     help="distinct pre-generated action batches cycled through (HBM resident)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the CPU baseline, the measured copy ceiling, the "
+                         "kernel-timing pass and its roofline figures, the whole-episode pass and the "
+                         "variants (the options below that shape them apply only with --full)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (every tensor of its observations, "
+                         "rewards and meta) as DIR/<name>.npy in float64, rank 0's envs; above "
+                         "%d MB in all, a fixed seeded sample of the envs (sample_env_index.npy)"
+                         % (DUMP_MAX_BYTES // 10 ** 6))
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-sample-envs", type=int, default=8192)
     ap.add_argument("--cpu-sample-steps", type=int, default=143)
@@ -157,7 +176,48 @@ def parse():
                          "step (off); bit-identical")
     ap.add_argument("--no-variants", action="store_true",
                     help="skip the fp32-storage variant line (N=1 only; never the headline)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps: at least one timed step")
+    return args
+
+
+def snapshot_outputs(step_out):
+    """Device copies of every tensor env.step returned (observations, rewards,
+    meta; the dones are host bools), keyed by their path in the returned dicts.
+    The step's outputs are views of buffers the next step or reset overwrites."""
+    obs, rew, _, meta = step_out
+    kept = {}
+
+    def walk(prefix, v):
+        if isinstance(v, dict):
+            for k in v:
+                walk(prefix + [str(k)], v[k])
+        elif torch.is_tensor(v):
+            kept[".".join(prefix)] = v.detach().clone()
+    walk(["obs"], obs)
+    walk(["reward"], rew)
+    walk(["meta"], meta)
+    return kept
+
+
+def dump_outputs(path, kept, n):
+    """--dump-outputs: the snapshot as path/<name>.npy, float64.  Above
+    DUMP_MAX_BYTES in all, the same seeded sample of the envs from every array
+    with an env axis (its sorted indices in sample_env_index.npy)."""
+    os.makedirs(path, exist_ok=True)
+    total = sum(t.numel() * 8 for t in kept.values())
+    idx = None
+    if total > DUMP_MAX_BYTES:
+        k = max(1, int(n * (DUMP_MAX_BYTES - 8 * n) / total))
+        idx = np.sort(np.random.default_rng(0).choice(n, size=k, replace=False))
+        np.save(os.path.join(path, "sample_env_index.npy"), idx.astype(np.float64))
+    for name, t in kept.items():
+        a = t.to(torch.float64).cpu().numpy()
+        if idx is not None and n in a.shape:
+            a = np.take(a, idx, axis=a.shape.index(n))
+        np.save(os.path.join(path, "".join(c if c.isalnum() or c in "._-" else "_" for c in name) + ".npy"),
+                np.ascontiguousarray(a))
 
 
 def f32_variant(conv, n, steps, warmup, pool_size, seed, dev):
@@ -452,7 +512,7 @@ def main():
         print(json.dumps(cpu_baseline(args.cpu_sample_envs, args.cpu_sample_steps, args.cpu_procs)))
         return
     cpu = None
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         # a child process, started before this one touches the GPU: the oracle's
         # imports and garbage never enter the timed process
         r = subprocess.run([sys.executable, os.path.abspath(__file__), "--cpu-baseline-only",
@@ -490,21 +550,27 @@ def main():
     step_count = 0
     host_t = []                                    # per-step host time of the last run() (diagnostics)
 
-    def run(k):
+    dump = bool(args.dump_outputs) and rank == 0
+    kept = []                                      # --dump-outputs: the last timed step's outputs
+
+    def run(k, keep=False):
         nonlocal step_count
         del host_t[:]
-        for _ in range(k):
+        for i in range(k):
             h0 = time.perf_counter()
-            _, _, dones, _ = env.step(packed[step_count % P])
+            out = env.step(packed[step_count % P])
             step_count += 1
-            if dones["__all__"]:
+            if out[2]["__all__"]:
+                if keep and i == k - 1:            # (the reset overwrites the observations)
+                    kept.append(snapshot_outputs(out))
                 env.reset()
             host_t.append(time.perf_counter() - h0)
+        return out if k else None
 
     from powergridworld_amd import _lib
-    # the measured HBM ceiling of this box (device copy) -- also brings the GPU
+    # --full: the measured HBM ceiling of this GPU (device copy) -- also brings it
     # out of its idle clocks after the host-only CPU baseline, before warmup
-    copy_gbs, torch_copy_gbs = stream_copy_gbs(dev, reps=100)
+    copy_gbs, torch_copy_gbs = stream_copy_gbs(dev, reps=100) if args.full else (None, None)
     # one cold episode: the env's FIRST reset() -- the
     # power flow's per-hour tables built on the device (first-iteration tables,
     # the response table with its certificates, node records) -- and the
@@ -537,7 +603,7 @@ def main():
         tdist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    run(args.steps)
+    last_out = run(args.steps, keep=dump)
     t_issued = time.perf_counter()
     torch.cuda.synchronize()
     if dist:
@@ -549,6 +615,49 @@ def main():
                    "note": "host side of the timed region on rank 0: time to issue the steps, then the wait for "
                            "the GPU; the slowest step's host time and its index"}
     elapsed = pgd.max_over_ranks(elapsed, dev)
+    if dump and not kept:
+        # device copies now, before any later pass overwrites the step's buffers
+        # (a last timed step that ended its episode was copied before its reset,
+        # inside the region: the one case in which --dump-outputs costs step time)
+        kept.append(snapshot_outputs(last_out))
+    total_envs = n * world
+    value = N_AGENTS * total_envs * args.steps / elapsed
+    head = {
+        "metric": "agent-env-steps/sec at batch 65536, 5-agent scenario, 1/2/4/8 MI355X",
+        "value": value,
+        "unit": "agent-env-steps/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic (seeded uniform actions pre-generated on device, synthetic "
+                "exogenous building data, IEEE-13 feeder + 8760-h loadshape)",
+        "config": {"workload": "C4: 5-agent coordinated buildings (building+PV+storage) "
+                               "+ IEEE-13 power flow + voltage-violation reward",
+                   "pf_convergence": conv,
+                   "batch_per_gpu": n, "global_batch": total_envs, "episode_steps": 286,
+                   "parallelism": "env-sharded x%d (no collective on the step path)" % world},
+        "episode_cold": {"steps": cold_steps, "ms": cold_total * 1e3, "reset_ms": cold_reset * 1e3,
+                         "ms_per_step": cold_total / cold_steps * 1e3,
+                         "value": N_AGENTS * total_envs * cold_steps / cold_total,
+                         "pf_table_build_s": env.pf_solver.od_resp_stats.get("build_s"),
+                         "note": "the env's first reset() (the power flow's per-hour tables built and "
+                                 "certified on the device) plus the whole first episode, first launches "
+                                 "included, no events"},
+        "host_region": host_region,
+    }
+    if not args.full:
+        if rank == 0:
+            if dump:
+                dump_outputs(args.dump_outputs, kept[0], n)
+            print(json.dumps(head))
+        if dist:
+            tdist.destroy_process_group()
+        return
     # kernel durations: a second pass right after the timed region, every launch
     # bracketed by HIP events on its own stream.  Kept out of `value`'s region:
     # an event-bracketed launch costs ~10 us of extra step time (measured: the
@@ -587,8 +696,6 @@ def main():
     # order once per episode, outside every timed region (RCCL at N>1)
     ep_stats = pgd.gather_episode_stats(torch.stack(
         [iters_last.double(), env.pf_solver.get_bus_voltage_by_name("675c").double()], 1))
-    total_envs = n * world
-    value = N_AGENTS * total_envs * args.steps / elapsed
     if rank == 0:
         avg_us = {KERNELS[k]: (tot[k] / cnt[k] * 1e3 if cnt[k] else None) for k in range(len(KERNELS))}
         it = iters_last.abs().double()
@@ -655,26 +762,9 @@ def main():
                 "frac": step_gbs / HBM_PEAK_GBS, "frac_measured_copy": step_gbs / copy_gbs,
                 "note": "algorithmic HBM bytes of the whole step (SURVEY 8(d): agents 312 B x 5 + "
                         "V675.3 8 B per env) / ms_per_step, per GPU"}
-        out = {
-            "metric": "agent-env-steps/sec at batch 65536, 5-agent scenario, 1/2/4/8 MI355X",
-            "value": value,
-            "unit": "agent-env-steps/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3,
+        out = dict(head)
+        out.update({
             "ms_per_step_episode": ep_elapsed / ep_steps * 1e3,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f64",
-            "data": "synthetic (seeded uniform actions pre-generated on device, synthetic "
-                    "exogenous building data, IEEE-13 feeder + 8760-h loadshape)",
-            "config": {"workload": "C4: 5-agent coordinated buildings (building+PV+storage) "
-                                   "+ IEEE-13 power flow + voltage-violation reward",
-                       "pf_convergence": conv,
-                       "batch_per_gpu": n, "global_batch": total_envs, "episode_steps": 286,
-                       "parallelism": "env-sharded x%d (no collective on the step path)" % world},
             "roofline": roof,
             "step_hbm": step,
             "stream_copy_gbs": copy_gbs,
@@ -687,21 +777,13 @@ def main():
                                       "`steps` steps right after the timed region (not inside it)"},
             "pf_iterations": {"mean": mean_it, "max": max_it, "wave_max_hist": wave_hist,
                               "unconverged_envs": unconverged},
-            "episode_cold": {"steps": cold_steps, "ms": cold_total * 1e3, "reset_ms": cold_reset * 1e3,
-                             "ms_per_step": cold_total / cold_steps * 1e3,
-                             "value": N_AGENTS * total_envs * cold_steps / cold_total,
-                             "pf_table_build_s": env.pf_solver.od_resp_stats.get("build_s"),
-                             "note": "the env's first reset() (the power flow's per-hour tables built and "
-                                     "certified on the device) plus the whole first episode, first launches "
-                                     "included, no events"},
-            "host_region": host_region,
             "episode": {"steps": ep_steps, "ms_per_step": ep_elapsed / ep_steps * 1e3,
                         "gathered_env_stats": int(ep_stats.shape[0]),
                         "value": N_AGENTS * total_envs * ep_steps / ep_elapsed,
                         "note": "one whole episode after the timed region: its %d steps and the "
                                 "env.reset() that ends it (reset kernels, predictor tables of the "
                                 "next hours), no events" % ep_steps},
-        }
+        })
         if world == 1 and not args.no_variants:
             other = "exact" if conv == "opendss" else "opendss"
             out["variants"] = {"graph8": graph_variant(env, packed, args.steps),
@@ -714,6 +796,8 @@ def main():
                                                                  packed, dev, od_table=False)
         if cpu is not None:
             out["cpu_baseline"] = cpu
+        if dump:
+            dump_outputs(args.dump_outputs, kept[0], n)
         print(json.dumps(out))
     if dist:
         tdist.destroy_process_group()

@@ -9,7 +9,7 @@ mkdir -p gpurun_out/ab
 for r in 1 2 3; do
   for v in A B; do
     if [ $v = A ]; then export PGW_LIB_PATH=$GRAFT_REPO_ROOT/$LIBA; else unset PGW_LIB_PATH; fi
-    timeout -k 10 300 python -u bench.py --steps $STEPS --warmup 20 --no-cpu-baseline --no-variants $EXTRA \
+    timeout -k 10 300 python -u bench.py --full --steps $STEPS --warmup 20 --no-cpu-baseline --no-variants $EXTRA \
       > gpurun_out/ab/${TAG}_$v$r.log 2>&1 || exit $?
     grep '"metric"' gpurun_out/ab/${TAG}_$v$r.log | python3 -c "
 import sys, json

@@ -7,7 +7,7 @@ VAR=$1; VA=$2; VB=$3; STEPS=${4:-286}
 mkdir -p gpurun_out/ab
 for r in 1 2; do
   for v in "$VA" "$VB"; do
-    env "$VAR=$v" timeout -k 10 300 python -u bench.py --steps $STEPS --warmup 20 --no-cpu-baseline --no-variants \
+    env "$VAR=$v" timeout -k 10 300 python -u bench.py --full --steps $STEPS --warmup 20 --no-cpu-baseline --no-variants \
       > gpurun_out/ab/env_${VAR}_${v}_$r.log 2>&1 || exit $?
     grep '"metric"' gpurun_out/ab/env_${VAR}_${v}_$r.log | python3 -c "
 import sys, json

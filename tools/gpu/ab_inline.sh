@@ -9,7 +9,7 @@ mkdir -p gpurun_out/ab
 for r in 1 2 3; do
   for v in "off 0" "on 1" "on 0"; do
     set -- $v
-    PGW_STEP_LIST=$2 timeout -k 10 300 python -u bench.py --steps $STEPS --warmup 20 --no-cpu-baseline --no-variants \
+    PGW_STEP_LIST=$2 timeout -k 10 300 python -u bench.py --full --steps $STEPS --warmup 20 --no-cpu-baseline --no-variants \
       --pf-split $1 > gpurun_out/ab/inl_$1_$2_$r.log 2>&1 || exit $?
     grep '"metric"' gpurun_out/ab/inl_$1_$2_$r.log | python3 -c "
 import sys, json

@@ -7,7 +7,7 @@ R=${1:-3}
 for r in $(seq 1 $R); do
   for L in new prev; do
     P=$GRAFT_REPO_ROOT/powergridworld_amd/libpgw.so; [ $L = prev ] && P=$GRAFT_REPO_ROOT/abprev/libpgw.so
-    PGW_LIB_PATH=$P timeout -k 10 300 python -u bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-variants 2>/dev/null | grep '^{' | python3 -c "
+    PGW_LIB_PATH=$P timeout -k 10 300 python -u bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-variants 2>/dev/null | grep '^{' | python3 -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 k = d['kernels']

@@ -1,9 +1,11 @@
-# Kernel-trace timeline of the bench (headline + variants): idle gaps between dispatches.
+# Kernel-trace timeline of the bench (--full: headline + variants): idle gaps
+# between dispatches.  Output goes to $PGW_OUT_DIR (default: bench_out/).
 set -o pipefail
-cd "$GRAFT_REPO_ROOT"; mkdir -p gpurun_out/prof
-export TMPDIR=/tmp
+cd "$(dirname "${BASH_SOURCE[0]}")/../.."
+ROOT=$PWD
+OUT=${PGW_OUT_DIR:-$ROOT/bench_out}; mkdir -p "$OUT/prof"
 TAG=${1:-gap}
-cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d "$GRAFT_REPO_ROOT/gpurun_out/prof/$TAG" -o run -- python3 "$GRAFT_REPO_ROOT/bench.py" --steps 100 --warmup 10 --no-cpu-baseline > "$GRAFT_REPO_ROOT/gpurun_out/prof_$TAG.log" 2>&1 || exit $?
-cd "$GRAFT_REPO_ROOT"
-f=$(find gpurun_out/prof/$TAG -name "*kernel_trace.csv" | head -1)
-python tools/gpu/gap_trace.py "$f" | tee gpurun_out/gaps_$TAG.txt
+cd "${TMPDIR:-/tmp}" && timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d "$OUT/prof/$TAG" -o run -- python3 "$ROOT/bench.py" --full --steps 100 --warmup 10 --no-cpu-baseline > "$OUT/prof_$TAG.log" 2>&1 || exit $?
+cd "$ROOT"
+f=$(find "$OUT/prof/$TAG" -name "*kernel_trace.csv" | head -1)
+python tools/gpu/gap_trace.py "$f" | tee "$OUT/gaps_$TAG.txt"
