@@ -753,6 +753,10 @@ struct StdAgentIn {
   double xs[5];     // building state x_k
   double soc;
 };
+// (the EARLY order's: with the building's consumption, which its power half hands to the rest)
+struct StdAgentInEarly : StdAgentIn {
+  double pc;
+};
 
 // Output slots handed to the store callback as soon as they are final.
 enum StdSlot { kSlotX = 0, kSlotSoc = 5, kSlotObs = 6, kSlotPower = 23, kSlotReward = 24 };
@@ -760,15 +764,27 @@ enum StdSlot { kSlotX = 0, kSlotSoc = 5, kSlotObs = 6, kSlotPower = 23, kSlotRew
 // One standard agent step for E envs at once (E = 1 or 2, computed stage by
 // stage so both envs' chains interleave); every output goes to
 // store(slot, v[E]) the moment it is final, so no output stays live.
-template <int E, class Store>
+// HALF 1, then HALF 2 (k_coord_step_od, a block barrier between the two calls):
+// the early-power order.  Half 1 turns the actions raw and forms the agent's
+// real power first -- it needs the raw actions and the SoC alone, no x_k,
+// temperature or observation -- through store(kSlotPower); half 2 is the
+// building step and the observations; `in` (StdAgentInEarly) carries the raw
+// actions, the stepped SoC and pc over.  Every output keeps its own operations
+// in their order; only independent chains change places, so the outputs are
+// the same bits.  HALF 0 (every other kernel) is the one-call order and
+// compiles to what it compiled to before the halves existed.
+template <int E, int HALF = 0, class In, class Store>
 __device__ __forceinline__ void std_agent_compute(const pgw_coord_params& p, const StdDerived& dv,
                                                   const pgw_coord_step_info& s, double pv_ob,
-                                                  StdAgentIn (&in)[E], Store&& store) {
+                                                  In (&in)[E], Store&& store) {
   const pgw_building_params& B = p.bld;
   double T[E][5], v[E];
+  double pc[E], rp_pv[E], power[E];
+  static_assert(HALF >= 0 && HALF <= 2, "HALF: 0 (one call), 1 (power half), 2 (the rest)");
+  constexpr bool EARLY = HALF != 0;
   // ---- building
 #pragma unroll
-  for (int q = 0; q < E; ++q) {
+  for (int q = 0; q < E && HALF != 2; ++q) {
     bool bad = false;
 #pragma unroll
     for (int j = 0; j < 6; ++j) {   // to_raw (utils.py:27-43) with host (hi - lo), (hi + lo)
@@ -777,8 +793,32 @@ __device__ __forceinline__ void std_agent_compute(const pgw_coord_params& p, con
                               : in[q].av[j];
     }
     if (B.rescale) oob_note(B.oob, bad);
+    if constexpr (!EARLY) {
 #pragma unroll
-    for (int z = 0; z < 5; ++z) T[q][z] = B.C[z] * in[q].xs[z] + B.mean[z];
+      for (int z = 0; z < 5; ++z) T[q][z] = B.C[z] * in[q].xs[z] + B.mean[z];
+    }
+  }
+  if constexpr (EARLY) {
+    if constexpr (HALF != 2) {      // MultiComponentEnv's sum (base.py:131-137), as below
+#pragma unroll
+      for (int q = 0; q < E; ++q) {
+        in[q].pc = building_p_consumed(in[q].av, s.ex_t.T_oa);
+        rp_pv[q] = pv_real_power(p.pv, in[q].av[6], s.pv_pmax);
+        power[q] = battery_step_rcp(p.bat, in[q].av[7], in[q].soc, dv.rcp_eta_d, dv.rcp_dt_h);
+        double agent_rp = 0.0;
+        agent_rp = agent_rp + in[q].pc;
+        agent_rp = agent_rp + rp_pv[q];
+        agent_rp = agent_rp + (-power[q]);
+        v[q] = agent_rp;
+      }
+      store(kSlotPower, v);
+    }
+    if constexpr (HALF == 1) return;
+#pragma unroll
+    for (int q = 0; q < E; ++q) {
+#pragma unroll
+      for (int z = 0; z < 5; ++z) T[q][z] = B.C[z] * in[q].xs[z] + B.mean[z];
+    }
   }
 #pragma unroll
   for (int z = 0; z < 5; ++z) {
@@ -798,12 +838,13 @@ __device__ __forceinline__ void std_agent_compute(const pgw_coord_params& p, con
     }
     store(kSlotX + z, v);
   }
-  double pc[E], r_bld[E];
+  double r_bld[E];
 #pragma unroll
   for (int q = 0; q < E; ++q) {
 #pragma unroll
     for (int z = 0; z < 5; ++z) T[q][z] = B.C[z] * in[q].xs[z] + B.mean[z];
-    pc[q] = building_p_consumed(in[q].av, s.ex_t.T_oa);
+    if constexpr (EARLY) pc[q] = in[q].pc;
+    else pc[q] = building_p_consumed(in[q].av, s.ex_t.T_oa);
     r_bld[q] = building_reward(B, T[q], s.ex_next.comfort_lb, s.ex_next.comfort_ub, pc[q],
                                exact_div(-pc[q], 12.0, 1.0 / 12.0));
   }
@@ -824,13 +865,14 @@ __device__ __forceinline__ void std_agent_compute(const pgw_coord_params& p, con
 #pragma unroll
   for (int q = 0; q < E; ++q) v[q] = pv_ob;
   store(kSlotObs + 15, v);
-  double rp_pv[E], power[E];
+  if constexpr (!EARLY) {
 #pragma unroll
-  for (int q = 0; q < E; ++q) rp_pv[q] = pv_real_power(p.pv, in[q].av[6], s.pv_pmax);
+    for (int q = 0; q < E; ++q) rp_pv[q] = pv_real_power(p.pv, in[q].av[6], s.pv_pmax);
+  }
   // ---- storage
 #pragma unroll
   for (int q = 0; q < E; ++q) {
-    power[q] = battery_step_rcp(p.bat, in[q].av[7], in[q].soc, dv.rcp_eta_d, dv.rcp_dt_h);
+    if constexpr (!EARLY) power[q] = battery_step_rcp(p.bat, in[q].av[7], in[q].soc, dv.rcp_eta_d, dv.rcp_dt_h);
     v[q] = in[q].soc;
   }
   store(kSlotSoc, v);
@@ -841,15 +883,17 @@ __device__ __forceinline__ void std_agent_compute(const pgw_coord_params& p, con
   }
   store(kSlotObs + 16, v);
   // MultiComponentEnv sums (base.py:131-137)
+  if constexpr (!EARLY) {
 #pragma unroll
-  for (int q = 0; q < E; ++q) {
-    double agent_rp = 0.0;
-    agent_rp = agent_rp + pc[q];
-    agent_rp = agent_rp + rp_pv[q];
-    agent_rp = agent_rp + (-power[q]);
-    v[q] = agent_rp;
+    for (int q = 0; q < E; ++q) {
+      double agent_rp = 0.0;
+      agent_rp = agent_rp + pc[q];
+      agent_rp = agent_rp + rp_pv[q];
+      agent_rp = agent_rp + (-power[q]);
+      v[q] = agent_rp;
+    }
+    store(kSlotPower, v);
   }
-  store(kSlotPower, v);
 #pragma unroll
   for (int q = 0; q < E; ++q) {
     double agent_rew = 0.0;
@@ -1711,6 +1755,8 @@ __device__ __forceinline__ void od_resp_at(const ODArgs& o, int rec, double t, d
 // od_resp_lookup for a solve whose only output is the node records' row: the
 // 96-byte node records alone (their headers decide exactly as the response
 // records', so the same envs are served, with the same counts).
+// (od_resp_v_cell / _load / _chain below are this function in three parts:
+// change the two together.)
 template <class OA>
 __device__ __forceinline__ bool od_resp_lookup_v(const OA& o, double P, double Q, double2& v, int& it) {
   constexpr int R2 = PGW_OD_VREC / 2;
@@ -1732,6 +1778,45 @@ __device__ __forceinline__ bool od_resp_lookup_v(const OA& o, double P, double Q
     r = next;
   }
   return false;
+}
+// The same lookup in three parts, for a caller that puts other work between
+// the first record's loads and their use (k_coord_step_od): the grid cell of
+// P, one record's loads, and the chain from the loaded first record (the same
+// decisions, at most kOdHops records).  A second copy of od_resp_lookup_v's
+// logic, kept because writing that function as cell + load + chain changed
+// k_coord_pf_od's code (9 970 -> 9 592 instructions, not measured): the two
+// must decide bit for bit alike, so change them together
+// (tests/test_gpu_step_overlap.py and test_od_split_step_bit_identical
+// compare them).
+struct ODVRec {
+  double2 h0, h1, h2, c0, c1, c2;
+};
+template <class OA>
+__device__ __forceinline__ bool od_resp_v_cell(const OA& o, double P, double Q, int& r) {
+  const double g = (P - o.resp_x0) * o.resp_inv_h;
+  if (!(Q == 0.0) || !(g >= 0.0 && g < (double)o.resp_nseg)) return false;
+  r = (int)g;
+  return true;
+}
+template <class OA>
+__device__ __forceinline__ ODVRec od_resp_v_load(const OA& o, int r) {
+  const double2* rec = reinterpret_cast<const double2*>(o.resp_v) + (int64_t)r * (PGW_OD_VREC / 2);
+  return {rec[0], rec[1], rec[2], rec[3], rec[4], rec[5]};
+}
+template <class OA>
+__device__ __forceinline__ bool od_resp_v_chain(const OA& o, double P, ODVRec rec, double2& v, int& it) {
+  for (int hop = 1;; ++hop) {                        // (hop: records loaded so far)
+    int k_it, next;
+    od_rec_meta(rec.h2.x, k_it, next);
+    if (P >= rec.h0.x && P <= rec.h0.y) {
+      if (k_it == 0) return false;
+      v = od_rec_j(rec.c0, rec.c1, rec.c2, (P - rec.h1.x) * rec.h1.y);
+      it = k_it;
+      return true;
+    }
+    if (next < 0 || hop >= kOdHops) return false;
+    rec = od_resp_v_load(o, next);
+  }
 }
 
 // The envs of the block the table does not cover: stage the check rows (the
@@ -2260,13 +2345,32 @@ __device__ int od_wave_solve(const ODWaveArgs& z_, const ODWaveShared& sh_, doub
 // Fused C4 step, OpenDSS rule with the hour's node records (pgw_pf_od.resp_v,
 // output row 0 the coordinated bus, no other row): the agents AND the power
 // flow's table lookup in one launch.  A block is n_agents waves over 64 envs;
-// wave a runs agent a's step (std_agent_compute, k_coord_agents_std's
-// operations and stores) and leaves its real power in LDS; after the block
-// barrier wave 0 sums the bus load in agent order (k_coord_pf_od's prologue),
-// looks the env up in the node records and, where the table serves it, writes
-// V675.3, the violation and the iteration count and leaves the reward share in
-// LDS; every wave then stores its agent's final reward (raw + (-share), as
-// k_coord_pf_od's epilogue).  Envs the table does not serve keep their raw
+// wave a runs agent a's step (std_agent_compute's halves: k_coord_agents_std's
+// operations and stores, the real power first) and leaves its real power in
+// LDS as soon as the actions and the SoC are in -- the block barrier comes
+// before the building step and every other store, so no wave waits there for
+// another's 24 stores.  Past it wave 0 sums the bus load in agent order
+// (k_coord_pf_od's prologue) and issues its env's node record after its x_k
+// stores; the gather's latency passes under its observations, and it then
+// finishes the lookup and, where the table serves the env, writes V675.3, the
+// violation and the iteration count and leaves the reward share in LDS; after
+// the second barrier every wave stores its agent's final reward (raw +
+// (-share), as k_coord_pf_od's epilogue).  (Before, the barrier stood after
+// all of a wave's stores and the lookup after the barrier: four waves idle
+// through a gather issued into the whole grid's stores.)
+// Measured (round 7, DESIGN.md section 5, profiles/r07/): rocprof mean 22.9 ->
+// 21.0 us, driver-shaped step 22.3-23.4 -> 21.1-21.7 us; the aims of 18.5 and
+// 20 us are missed.  Of the 3.9 us still over k_coord_agents_std (17.1 us),
+// timing-only runs without the lookup (PGW_STEP_NOLOOKUP) put 1.2-1.5 us on
+// the lookup link (parent 1.5-1.7: the gather is issued early, but wave 0's
+// chain, square root, three stores and LDS writes still stand before the
+// second barrier, and every reward store behind that) and about 2.6 us on the
+// five-wave block with its two barriers whatever the lookup does.  The early
+// barrier and the scratch-free build gave 1.3-1.6 us of the 1.9 us gained.
+// The other form tried -- every wave looking the env up itself, no second
+// barrier -- ran 2.5-3.4 us slower than this one and was dropped
+// (profiles/r07/step_all_waves_lookup_dropped.txt).
+// Envs the table does not serve keep their raw
 // rewards and are appended to b.od_list (count b.od_count[parity]) for
 // k_coord_pf_od_list, launched next.  Block 0 zeroes the other parity's count
 // (the next step's list).  Bit-identical to k_coord_agents_std + k_coord_pf_od.
@@ -2274,8 +2378,10 @@ __device__ int od_wave_solve(const ODWaveArgs& z_, const ODWaveShared& sh_, doub
 // for the next launch's boundary to write back.
 // INL (the default one-launch step): the lookup wave solves the envs the table
 // leaves itself (od_wave_solve), one at a time, and nothing is listed -- the
-// step is this launch alone.  (7 waves per SIMD: 71 VGPRs, 5 blocks per CU;
-// at 6 the kernel ran 0.3 us slower, profiles/r06/ab_one_launch_step.txt.)
+// step is this launch alone.  (7 waves per SIMD: 71 VGPRs, no scratch -- the
+// raw reward waits in LDS through the wave solve --, 5 blocks per CU,
+// profiles/r07/step_od_resource_usage.txt; at 6 the round-6 kernel ran 0.3 us
+// slower, profiles/r06/ab_one_launch_step.txt.)
 // (the step's parameters and the wave solve's constants: one first argument,
 // read in place from the kernarg segment)
 struct StepOdArgs {
@@ -2300,48 +2406,65 @@ __global__ void __launch_bounds__(64 * PGW_MAX_AGENTS) __attribute__((amdgpu_wav
   __shared__ double s_share[64];
   __shared__ int s_served[64];
   if (blockIdx.x == 0 && threadIdx.x == 0) b.od_count[(b.od_parity & 1) ^ 1] = 0;
+  // (a local copy: a reference to the by-value kernel argument would put it
+  // in a private-memory frame)
+  const ODVLook ol = {o.resp_v, o.resp_x0, o.resp_inv_h, o.resp_nseg, 0};
   double rw = 0.0;
+  StdAgentInEarly in[1];
+  double* xp = b.x + (int64_t)a * 5 * n + e;
+  double* socp = b.soc + (int64_t)a * n + e;
+  // the agent's real power first: it waits for the actions and the SoC alone
+  // (the x_k loads, issued last, stay in flight across the barrier)
   if (valid) {
-    StdAgentIn in[1];
     const double* ap = b.action.ptr + a * b.act_stride_agent + e * b.action.s_env;
 #pragma unroll
     for (int j = 0; j < 8; ++j) in[0].av[j] = ld_act(ap + j * b.action.s_dim);
-    double* xp = b.x + (int64_t)a * 5 * n + e;
+    in[0].soc = *socp;
 #pragma unroll
     for (int z = 0; z < 5; ++z) in[0].xs[z] = xp[z * n];
-    double* socp = b.soc + (int64_t)a * n + e;
-    in[0].soc = *socp;
+    std_agent_compute<1, 1>(p, dv, s, pv_ob, in, [&](int, const double (&v)[1]) {
+      s_pow[a][lane] = v[0];
+      put(b.agent_power + (int64_t)a * n + e, v[0]);
+    });
+  }
+  __syncthreads();
+  // the building step, the observations and their stores; wave 0 sums the bus
+  // load and issues its env's first node record after the last x_k store (the
+  // fewest values live there), so the gather's latency passes under the
+  // observations' arithmetic and stores
+  double pc = 0.0;
+  ODVRec rec;                                        // (read only where cell)
+  bool cell = false;
+  if (valid) {
     double* op = b.obs.ptr + a * b.obs_stride_agent + e * b.obs.s_env;
-    std_agent_compute<1>(p, dv, s, pv_ob, in, [&](int slot, const double (&v)[1]) {
-      if (slot < kSlotSoc) put(xp + slot * n, v[0]);
-      else if (slot == kSlotSoc) put(socp, v[0]);
+    std_agent_compute<1, 2>(p, dv, s, pv_ob, in, [&](int slot, const double (&v)[1]) {
+      if (slot < kSlotSoc) {
+        put(xp + slot * n, v[0]);
+        if (slot == kSlotX + 4 && a == 0) {          // (wave-uniform)
+          // the bus load of controllable slot 0 in agent order (k_coord_pf_od: 0 + p0 + p1 ...)
+#pragma unroll
+          for (int ag = 0; ag < PGW_MAX_AGENTS; ++ag) {
+            const int cs = ag < c.n_agents ? c.agent_ctrl[ag] : -1;
+            const double pa = ag < c.n_agents ? s_pow[ag][lane] * 1.0 : 0.0;
+            pc = (cs == 0) ? pc + pa : pc;
+          }
+          int r = 0;
+          cell = !o.timing_only && od_resp_v_cell(ol, pc, 0.0, r);
+          if (cell) rec = od_resp_v_load(ol, r);
+        }
+      } else if (slot == kSlotSoc) put(socp, v[0]);
       else if (slot < kSlotPower) {
         if constexpr (WT) st_wt(op + (slot - kSlotObs) * b.obs.s_dim, v[0]);
         else st_obs(op + (slot - kSlotObs) * b.obs.s_dim, v[0]);
-      } else if (slot == kSlotPower) {
-        put(b.agent_power + (int64_t)a * n + e, v[0]);
-        s_pow[a][lane] = v[0];
       } else {
         rw = v[0];
       }
     });
   }
-  __syncthreads();
   if (a == 0) {
-    // the bus load of controllable slot 0 in agent order (k_coord_pf_od: 0 + p0 + p1 ...)
-    double pc = 0.0;
-#pragma unroll
-    for (int ag = 0; ag < PGW_MAX_AGENTS; ++ag) {
-      const int slot = ag < c.n_agents ? c.agent_ctrl[ag] : -1;
-      const double rp = (valid && ag < c.n_agents) ? s_pow[ag][lane] * 1.0 : 0.0;
-      pc = (slot == 0) ? pc + rp : pc;
-    }
     double2 vf = make_double2(0.0, 0.0);
     int it = 0;
-    // (a local copy: a reference to the by-value kernel argument would put it
-    // in a private-memory frame)
-    const ODVLook ol = {o.resp_v, o.resp_x0, o.resp_inv_h, o.resp_nseg, 0};
-    bool served = valid && !o.timing_only && od_resp_lookup_v(ol, pc, 0.0, vf, it);
+    bool served = valid && cell && od_resp_v_chain(ol, pc, rec, vf, it);
     if constexpr (INL) {
       // the envs the table left: the wave's snap solve, one env at a time
       // (the usual wave has none); their node-0 voltage then takes the served
@@ -2351,17 +2474,22 @@ __global__ void __launch_bounds__(64 * PGW_MAX_AGENTS) __attribute__((amdgpu_wav
       if (left) {                                    // (uniform) counted as the list form counts them
         if (lane == 0) atomicAdd(b.od_count + (b.od_parity & 1), __popcll(left));
         od_wave_stage(z, s_solve);
-      }
-      while (left) {                                 // (uniform)
-        const int L = __builtin_ctzll(left);
-        left &= left - 1;
-        double v0r, v0i;
-        const int its = od_wave_solve(z, s_solve, wave_bcast(pc, L), 0.0, v0r, v0i);
-        if (lane == L) {
-          vf = make_double2(v0r, v0i);
-          it = its;
-          served = true;
-        }
+        // (the raw reward waits in LDS: live in a register through the solve
+        // it is spilled to scratch on every wave's path)
+        __shared__ double s_rw[64];
+        s_rw[lane] = rw;
+        do {
+          const int L = __builtin_ctzll(left);
+          left &= left - 1;
+          double v0r, v0i;
+          const int its = od_wave_solve(z, s_solve, wave_bcast(pc, L), 0.0, v0r, v0i);
+          if (lane == L) {
+            vf = make_double2(v0r, v0i);
+            it = its;
+            served = true;
+          }
+        } while (left);
+        rw = s_rw[lane];
       }
     }
     double share = 0.0;
