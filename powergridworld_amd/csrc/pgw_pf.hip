@@ -2344,31 +2344,46 @@ __device__ int od_wave_solve(const ODWaveArgs& z_, const ODWaveShared& sh_, doub
 
 // Fused C4 step, OpenDSS rule with the hour's node records (pgw_pf_od.resp_v,
 // output row 0 the coordinated bus, no other row): the agents AND the power
-// flow's table lookup in one launch.  A block is n_agents waves over 64 envs;
-// wave a runs agent a's step (std_agent_compute's halves: k_coord_agents_std's
-// operations and stores, the real power first) and leaves its real power in
-// LDS as soon as the actions and the SoC are in -- the block barrier comes
-// before the building step and every other store, so no wave waits there for
-// another's 24 stores.  Past it wave 0 sums the bus load in agent order
-// (k_coord_pf_od's prologue) and issues its env's node record after its x_k
-// stores; the gather's latency passes under its observations, and it then
-// finishes the lookup and, where the table serves the env, writes V675.3, the
-// violation and the iteration count and leaves the reward share in LDS; after
-// the second barrier every wave stores its agent's final reward (raw +
-// (-share), as k_coord_pf_od's epilogue).  (Before, the barrier stood after
-// all of a wave's stores and the lookup after the barrier: four waves idle
-// through a gather issued into the whole grid's stores.)
-// Measured (round 7, DESIGN.md section 5, profiles/r07/): rocprof mean 22.9 ->
-// 21.0 us, driver-shaped step 22.3-23.4 -> 21.1-21.7 us; the aims of 18.5 and
-// 20 us are missed.  Of the 3.9 us still over k_coord_agents_std (17.1 us),
-// timing-only runs without the lookup (PGW_STEP_NOLOOKUP) put 1.2-1.5 us on
-// the lookup link (parent 1.5-1.7: the gather is issued early, but wave 0's
-// chain, square root, three stores and LDS writes still stand before the
-// second barrier, and every reward store behind that) and about 2.6 us on the
-// five-wave block with its two barriers whatever the lookup does.  The early
-// barrier and the scratch-free build gave 1.3-1.6 us of the 1.9 us gained.
-// The other form tried -- every wave looking the env up itself, no second
-// barrier -- ran 2.5-3.4 us slower than this one and was dropped
+// flow's table lookup in one launch.  A block is n_agents + 1 waves over 64
+// envs: one wave per agent and the lookup wave (the last).  The two kinds run
+// separate code and meet at the block's two barriers.
+// Wave a < n_agents runs agent a's step (std_agent_compute's halves:
+// k_coord_agents_std's operations and stores, the real power first) and
+// leaves its real power in LDS as soon as the actions and the SoC are in --
+// the first barrier comes before the building step and every other store, so
+// no wave waits there for another's 24 stores (the x_k loads stay in flight
+// across it).  Past it the wave runs the building step, the x_k, SoC and
+// observation stores and the raw reward, and after the second barrier stores
+// its agent's final reward (raw + (-share), as k_coord_pf_od's epilogue).
+// The lookup wave touches no global memory before the first barrier (its
+// scalar arguments are in registers by then).  Past it it sums the bus load
+// in agent order (k_coord_pf_od's prologue: 0 + p0 + p1 ...), finds the cell
+// and gathers the node record -- the only entries of its memory queue, so the
+// chain waits for the gather alone, beside the agent waves' arithmetic and
+// store issue --, finishes the lookup, solves or lists the envs the table
+// does not serve, writes V675.3, the violation and the iteration count and
+// leaves the reward share and the served flag in LDS for the second barrier.
+// (Round 7 had wave 0 do both: vmcnt counts loads and stores together, so its
+// chain could not start before 12 of the 18 stores issued after the gather
+// were acknowledged, nor finish before all were, with every CU streaming
+// stores -- and all five reward stores stood behind that at the second
+// barrier.  Round 6 had the barrier after all of a wave's stores and the
+// lookup after it.)
+// One body with `if (lookup wave) .. else ..` between two shared barriers was
+// compiled and not kept: the agents' values carried over the first barrier
+// were spilled (116-196 B of scratch per lane, the loads of half 1 serialised
+// behind the spills); as two bodies, each with its own pair of s_barrier --
+// the hardware counts the block's waves whichever instruction each arrives
+// at, and the branch is scalar -- the kernel has no scratch
+// (profiles/r08/step_od_resource_usage.txt).
+// Measured (round 8, DESIGN.md section 5, profiles/r08/): rocprof mean 21.3 ->
+// 20.3 us, the 572-step bench 21.6-22.1 -> 20.6-21.0 us per step, below the
+// parent in every one of five alternated pairs (median difference 1.04 us,
+// the parent's own spread 0.54).  Round 7's figures: 22.9 -> 21.0 us, of the
+// 3.9 us then left over k_coord_agents_std (17.1 us) 1.2-1.5 us on the lookup
+// link and about 2.6 us on the five-wave block with its two barriers whatever
+// the lookup does.  The other form tried then -- every wave looking the env
+// up itself, no second barrier -- ran 2.5-3.4 us slower and was dropped
 // (profiles/r07/step_all_waves_lookup_dropped.txt).
 // Envs the table does not serve keep their raw
 // rewards and are appended to b.od_list (count b.od_count[parity]) for
@@ -2378,9 +2393,9 @@ __device__ int od_wave_solve(const ODWaveArgs& z_, const ODWaveShared& sh_, doub
 // for the next launch's boundary to write back.
 // INL (the default one-launch step): the lookup wave solves the envs the table
 // leaves itself (od_wave_solve), one at a time, and nothing is listed -- the
-// step is this launch alone.  (7 waves per SIMD: 71 VGPRs, no scratch -- the
-// raw reward waits in LDS through the wave solve --, 5 blocks per CU,
-// profiles/r07/step_od_resource_usage.txt; at 6 the round-6 kernel ran 0.3 us
+// step is this launch alone.  (7 waves per SIMD: 72 VGPRs, no scratch; at the
+// headline shape 4 blocks = 24 waves per CU, 6 per SIMD, one round;
+// profiles/r08/step_od_resource_usage.txt; at 6 the round-6 kernel ran 0.3 us
 // slower, profiles/r06/ab_one_launch_step.txt.)
 // (the step's parameters and the wave solve's constants: one first argument,
 // read in place from the kernarg segment)
@@ -2389,7 +2404,7 @@ struct StepOdArgs {
   ODWaveArgs z;
 };
 template <bool WT, bool INL>
-__global__ void __launch_bounds__(64 * PGW_MAX_AGENTS) __attribute__((amdgpu_waves_per_eu(7))) k_coord_step_od(StepOdArgs A_, pgw_coord_step_info s,
+__global__ void __launch_bounds__(64 * (PGW_MAX_AGENTS + 1)) __attribute__((amdgpu_waves_per_eu(7))) k_coord_step_od(StepOdArgs A_, pgw_coord_step_info s,
                                                                        int64_t n, pgw_coord_buffers b, double pv_ob,
                                                                        StdDerived dv, CoordPFArgs c, ODVLook o) {
   auto put = [](auto* q, auto v) {
@@ -2400,127 +2415,140 @@ __global__ void __launch_bounds__(64 * PGW_MAX_AGENTS) __attribute__((amdgpu_wav
   const pgw_coord_params& p = A.p;
   const ODWaveArgs& z = A.z;
   const int a = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  // (wave-uniform, made scalar) the lookup wave: the one after the agents'
+  const bool look = __builtin_amdgcn_readfirstlane(a) == c.n_agents;
   const int64_t e = (int64_t)blockIdx.x * 64 + lane;
   const bool valid = e < n;
   __shared__ double s_pow[PGW_MAX_AGENTS][64];
   __shared__ double s_share[64];
   __shared__ int s_served[64];
-  if (blockIdx.x == 0 && threadIdx.x == 0) b.od_count[(b.od_parity & 1) ^ 1] = 0;
+  // The two kinds of wave run separate code, each with its own two barrier
+  // instructions: the hardware barrier counts the block's waves whichever
+  // instruction each arrives at, and a wave takes one side whole (a scalar
+  // branch), so no value of one side is live on the other.
+  if (!look) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) b.od_count[(b.od_parity & 1) ^ 1] = 0;
+    double rw = 0.0;
+    StdAgentInEarly in[1];
+    double* xp = b.x + (int64_t)a * 5 * n + e;
+    double* socp = b.soc + (int64_t)a * n + e;
+    // the agent's real power first: it waits for the actions and the SoC alone
+    // (the x_k loads, issued last, stay in flight across the barrier)
+    if (valid) {
+      const double* ap = b.action.ptr + a * b.act_stride_agent + e * b.action.s_env;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) in[0].av[j] = ld_act(ap + j * b.action.s_dim);
+      in[0].soc = *socp;
+#pragma unroll
+      for (int z = 0; z < 5; ++z) in[0].xs[z] = xp[z * n];
+      std_agent_compute<1, 1>(p, dv, s, pv_ob, in, [&](int, const double (&v)[1]) {
+        s_pow[a][lane] = v[0];
+        put(b.agent_power + (int64_t)a * n + e, v[0]);
+      });
+    }
+    __syncthreads();
+    // the building step, the observations and their stores
+    if (valid) {
+      double* op = b.obs.ptr + a * b.obs_stride_agent + e * b.obs.s_env;
+      std_agent_compute<1, 2>(p, dv, s, pv_ob, in, [&](int slot, const double (&v)[1]) {
+        if (slot < kSlotSoc) put(xp + slot * n, v[0]);
+        else if (slot == kSlotSoc) put(socp, v[0]);
+        else if (slot < kSlotPower) {
+          if constexpr (WT) st_wt(op + (slot - kSlotObs) * b.obs.s_dim, v[0]);
+          else st_obs(op + (slot - kSlotObs) * b.obs.s_dim, v[0]);
+        } else {
+          rw = v[0];
+        }
+      });
+    }
+    __syncthreads();
+    if (!valid) return;
+    const bool fin = c.coordinated && s_served[lane];
+    put(b.reward + (int64_t)a * n + e, fin ? rw + (-s_share[lane]) : rw);
+    return;
+  }
+  // The lookup wave: no global memory access before the first barrier.
   // (a local copy: a reference to the by-value kernel argument would put it
   // in a private-memory frame)
-  const ODVLook ol = {o.resp_v, o.resp_x0, o.resp_inv_h, o.resp_nseg, 0};
-  double rw = 0.0;
-  StdAgentInEarly in[1];
-  double* xp = b.x + (int64_t)a * 5 * n + e;
-  double* socp = b.soc + (int64_t)a * n + e;
-  // the agent's real power first: it waits for the actions and the SoC alone
-  // (the x_k loads, issued last, stay in flight across the barrier)
-  if (valid) {
-    const double* ap = b.action.ptr + a * b.act_stride_agent + e * b.action.s_env;
+  ODVLook ol = {o.resp_v, o.resp_x0, o.resp_inv_h, o.resp_nseg, 0};
+  // (the scalars the lookup starts with, in registers before the barrier: the
+  // wave idles there, and their kernarg loads would otherwise wait behind it)
+  int ctrl[PGW_MAX_AGENTS];
 #pragma unroll
-    for (int j = 0; j < 8; ++j) in[0].av[j] = ld_act(ap + j * b.action.s_dim);
-    in[0].soc = *socp;
-#pragma unroll
-    for (int z = 0; z < 5; ++z) in[0].xs[z] = xp[z * n];
-    std_agent_compute<1, 1>(p, dv, s, pv_ob, in, [&](int, const double (&v)[1]) {
-      s_pow[a][lane] = v[0];
-      put(b.agent_power + (int64_t)a * n + e, v[0]);
-    });
+  for (int ag = 0; ag < PGW_MAX_AGENTS; ++ag) {
+    ctrl[ag] = c.agent_ctrl[ag];
+    asm volatile("" : "+s"(ctrl[ag]));
   }
+  asm volatile("" : "+s"(ol.resp_x0), "+s"(ol.resp_inv_h), "+s"(ol.resp_nseg));
   __syncthreads();
-  // the building step, the observations and their stores; wave 0 sums the bus
-  // load and issues its env's first node record after the last x_k store (the
-  // fewest values live there), so the gather's latency passes under the
-  // observations' arithmetic and stores
+  // the bus load of controllable slot 0 in agent order (k_coord_pf_od: 0 + p0
+  // + p1 ...), the grid cell and the node record -- the only entries of this
+  // wave's memory queue, so the chain waits for the gather alone and runs
+  // beside the agent waves' arithmetic and store issue
   double pc = 0.0;
   ODVRec rec;                                        // (read only where cell)
   bool cell = false;
   if (valid) {
-    double* op = b.obs.ptr + a * b.obs_stride_agent + e * b.obs.s_env;
-    std_agent_compute<1, 2>(p, dv, s, pv_ob, in, [&](int slot, const double (&v)[1]) {
-      if (slot < kSlotSoc) {
-        put(xp + slot * n, v[0]);
-        if (slot == kSlotX + 4 && a == 0) {          // (wave-uniform)
-          // the bus load of controllable slot 0 in agent order (k_coord_pf_od: 0 + p0 + p1 ...)
 #pragma unroll
-          for (int ag = 0; ag < PGW_MAX_AGENTS; ++ag) {
-            const int cs = ag < c.n_agents ? c.agent_ctrl[ag] : -1;
-            const double pa = ag < c.n_agents ? s_pow[ag][lane] * 1.0 : 0.0;
-            pc = (cs == 0) ? pc + pa : pc;
-          }
-          int r = 0;
-          cell = !o.timing_only && od_resp_v_cell(ol, pc, 0.0, r);
-          if (cell) rec = od_resp_v_load(ol, r);
+    for (int ag = 0; ag < PGW_MAX_AGENTS; ++ag) {
+      const int cs = ag < c.n_agents ? ctrl[ag] : -1;
+      const double pa = ag < c.n_agents ? s_pow[ag][lane] * 1.0 : 0.0;
+      pc = (cs == 0) ? pc + pa : pc;
+    }
+    int r = 0;
+    cell = !o.timing_only && od_resp_v_cell(ol, pc, 0.0, r);
+    if (cell) rec = od_resp_v_load(ol, r);
+  }
+  double2 vf = make_double2(0.0, 0.0);
+  int it = 0;
+  bool served = valid && cell && od_resp_v_chain(ol, pc, rec, vf, it);
+  if constexpr (INL) {
+    // the envs the table left: the wave's snap solve, one env at a time
+    // (the usual wave has none); their node-0 voltage then takes the served
+    // path's place (the same operations as k_coord_pf_od's epilogue)
+    __shared__ ODWaveShared s_solve;
+    uint64_t left = __ballot(valid && !served && !o.timing_only);
+    if (left) {                                      // (uniform) counted as the list form counts them
+      if (lane == 0) atomicAdd(b.od_count + (b.od_parity & 1), __popcll(left));
+      od_wave_stage(z, s_solve);
+      do {
+        const int L = __builtin_ctzll(left);
+        left &= left - 1;
+        double v0r, v0i;
+        const int its = od_wave_solve(z, s_solve, wave_bcast(pc, L), 0.0, v0r, v0i);
+        if (lane == L) {
+          vf = make_double2(v0r, v0i);
+          it = its;
+          served = true;
         }
-      } else if (slot == kSlotSoc) put(socp, v[0]);
-      else if (slot < kSlotPower) {
-        if constexpr (WT) st_wt(op + (slot - kSlotObs) * b.obs.s_dim, v[0]);
-        else st_obs(op + (slot - kSlotObs) * b.obs.s_dim, v[0]);
-      } else {
-        rw = v[0];
-      }
-    });
+      } while (left);
+    }
   }
-  if (a == 0) {
-    double2 vf = make_double2(0.0, 0.0);
-    int it = 0;
-    bool served = valid && cell && od_resp_v_chain(ol, pc, rec, vf, it);
-    if constexpr (INL) {
-      // the envs the table left: the wave's snap solve, one env at a time
-      // (the usual wave has none); their node-0 voltage then takes the served
-      // path's place (the same operations as k_coord_pf_od's epilogue)
-      __shared__ ODWaveShared s_solve;
-      uint64_t left = __ballot(valid && !served && !o.timing_only);
-      if (left) {                                    // (uniform) counted as the list form counts them
-        if (lane == 0) atomicAdd(b.od_count + (b.od_parity & 1), __popcll(left));
-        od_wave_stage(z, s_solve);
-        // (the raw reward waits in LDS: live in a register through the solve
-        // it is spilled to scratch on every wave's path)
-        __shared__ double s_rw[64];
-        s_rw[lane] = rw;
-        do {
-          const int L = __builtin_ctzll(left);
-          left &= left - 1;
-          double v0r, v0i;
-          const int its = od_wave_solve(z, s_solve, wave_bcast(pc, L), 0.0, v0r, v0i);
-          if (lane == L) {
-            vf = make_double2(v0r, v0i);
-            it = its;
-            served = true;
-          }
-        } while (left);
-        rw = s_rw[lane];
-      }
+  double share = 0.0;
+  if (served) {
+    const double v0 = sqrt(fma(vf.y, vf.y, vf.x * vf.x));
+    if (b.v_out) put(b.v_out + e, v0);
+    if (b.iters) put(b.iters + e, (int32_t)it);
+    if (c.coordinated) {
+      const double vv = pymax(pymax(0.0, c.vv_lo - v0), v0 - c.vv_hi);
+      if (b.vv) put(b.vv + e, vv);
+      share = (vv * c.vv_penalty) / (double)c.n_agents;
     }
-    double share = 0.0;
-    if (served) {
-      const double v0 = sqrt(fma(vf.y, vf.y, vf.x * vf.x));
-      if (b.v_out) put(b.v_out + e, v0);
-      if (b.iters) put(b.iters + e, (int32_t)it);
-      if (c.coordinated) {
-        const double vv = pymax(pymax(0.0, c.vv_lo - v0), v0 - c.vv_hi);
-        if (b.vv) put(b.vv + e, vv);
-        share = (vv * c.vv_penalty) / (double)c.n_agents;
-      }
-    }
-    // the envs left to the solve: one list slot each, one atomic per wave
-    // (INL: none -- every valid env was served or solved above)
-    const bool need = !INL && valid && !served && !o.timing_only;
-    const uint64_t m = __ballot(need);
-    if (m) {
-      const int first = __builtin_ctzll(m);
-      int base = 0;
-      if (lane == first) base = atomicAdd(b.od_count + (b.od_parity & 1), __popcll(m));
-      base = __shfl(base, first);
-      if (need) b.od_list[base + __popcll(m & ((1ull << lane) - 1ull))] = (int32_t)e;
-    }
-    s_share[lane] = share;
-    s_served[lane] = served ? 1 : 0;
   }
+  // the envs left to the solve: one list slot each, one atomic per wave
+  // (INL: none -- every valid env was served or solved above)
+  const bool need = !INL && valid && !served && !o.timing_only;
+  const uint64_t m = __ballot(need);
+  if (m) {
+    const int first = __builtin_ctzll(m);
+    int base = 0;
+    if (lane == first) base = atomicAdd(b.od_count + (b.od_parity & 1), __popcll(m));
+    base = __shfl(base, first);
+    if (need) b.od_list[base + __popcll(m & ((1ull << lane) - 1ull))] = (int32_t)e;
+  }
+  s_share[lane] = share;
+  s_served[lane] = served ? 1 : 0;
   __syncthreads();
-  if (!valid) return;
-  const bool fin = c.coordinated && s_served[lane];
-  put(b.reward + (int64_t)a * n + e, fin ? rw + (-s_share[lane]) : rw);
 }
 
 // The snap solve of the envs k_coord_step_od appended to its list (the table
@@ -3134,7 +3162,9 @@ static int32_t coord_step(const pgw_coord_params* p, const pgw_pf_params* pf, co
       if (std_layout && o.resp_v && o.resp_v_row == 0 && pf->n_out == 1 && p->vv_row == 0) {
         const ODVLook lk = {o.resp_v, o.resp_x0, o.resp_inv_h, o.resp_nseg, g_step_nolookup ? 1 : 0};
         const StepOdArgs sa = {*p, make_wave_args(a, o, *pf, *pft)};
-        const dim3 grid((unsigned)((n + 63) / 64)), block(64 * p->n_agents);
+        // a block: one wave per agent and the lookup wave, over 64 envs
+        static_assert(64 * (PGW_MAX_AGENTS + 1) <= 1024, "k_coord_step_od: a block of PGW_MAX_AGENTS + 1 waves");
+        const dim3 grid((unsigned)((n + 63) / 64)), block(64 * (p->n_agents + 1));
         if (!g_step_list) {                         // the one-launch step
           if (g_step_wt)
             launch_timed(PGW_T_COORD_AGENTS, k_coord_step_od<true, true>, grid, block, st, sa, *s, n, b, pv_ob,
