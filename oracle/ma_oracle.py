@@ -24,13 +24,18 @@ class CoordinatedOracle:
     VOLTAGE_LIMITS = (0.95, 1.05)
     VV_UNIT_PENALTY = 1e4
 
-    def __init__(self, K, n_agents=5, sys_load=1.2, exo=None, bus_node="675.3", bus_load="675c"):
+    def __init__(self, K, n_agents=5, sys_load=1.2, exo=None, bus_node="675.3", bus_load="675c",
+                 storage_config=None, pv_scaling_factor=40.):
+        """storage_config: the batteries' keyword arguments (make_c4_config's
+        storage_config; default the C4 battery)."""
         exo = synthetic_exogenous_frame() if exo is None else exo
         self.K, self.n = K, n_agents
+        storage_config = {"max_power": 15., "storage_range": (3., 50.)} if storage_config is None \
+            else dict(storage_config)
         self.agents = [MCOracle([
             ("building", BuildingOracle(K, exo)),
-            ("pv", PVOracle(K, profile_csv="pv_profile.csv", scaling_factor=40.)),
-            ("storage", BatteryOracle(K, max_power=15., storage_range=(3., 50.)))])
+            ("pv", PVOracle(K, profile_csv="pv_profile.csv", scaling_factor=pv_scaling_factor)),
+            ("storage", BatteryOracle(K, **storage_config))])
             for _ in range(n_agents)]
         self.pf = BatchedPF(system_load_rescale_factor=sys_load)
         self.node = self.pf.feeder.idx[bus_node]

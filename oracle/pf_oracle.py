@@ -419,7 +419,7 @@ class Feeder:
         return V, iters
 
     def snap_opendss(self, load_kw, load_kvar, yprim_kw=None, yprim_kvar=None,
-                     tol=1e-4, min_iter=2, max_iter=15, V_start=None):
+                     tol=1e-4, min_iter=2, max_iter=15, V_start=None, trace=None):
         """OpenDSS's own snap solve, restated from its published solution method
         (Solution.pas SolveSnap -> SolveCircuit -> DoPFLOWsolution; the
         reference reaches it through ``Solve mode=snap``, opendss.py:134):
@@ -448,7 +448,14 @@ class Feeder:
         ``Solve`` (pass ``spec`` base values, shape (n_loads,)).  Pass None to
         stamp the step's own powers instead (the alternative reading, per env).
 
-        Returns (V nodes (K, n), iterations (K,))."""
+        ``trace``: a list that receives every iteration's tested quantity, the
+        (K, n) changes | |V_new| - |V_old| | / Vbase_node of all envs (those
+        already stopped included), for tests that ask which node decided.
+
+        Returns (V nodes (K, n), iterations (K,)); ``self.last_converged`` (K,)
+        bool then tells whether each env's last iteration passed the test -- an
+        env at ``max_iter`` either converged exactly there or was stopped by the
+        cap (the kernels report the latter as a negative count)."""
         load_kw = np.atleast_2d(np.asarray(load_kw, float))
         load_kvar = np.atleast_2d(np.asarray(load_kvar, float))
         K = load_kw.shape[0]
@@ -473,18 +480,24 @@ class Feeder:
         vbn = self.kv_ln * 1000.0
         iters = np.zeros(K, int)
         active = np.ones(K, bool)
+        passed = np.zeros(K, bool)
         for it in range(1, max_iter + 1):
             U = V @ C.T
             IL = self.load_currents(U, W_ph, var_ph)
             J = self.I_src + (yeq * U - IL) @ C
             Vn = solve(J)
-            err = np.max(np.abs(np.abs(Vn) - np.abs(V)) / vbn, axis=1)
+            chg = np.abs(np.abs(Vn) - np.abs(V)) / vbn
+            if trace is not None:
+                trace.append(chg)
+            err = np.max(chg, axis=1)
             V = np.where(active[:, None], Vn, V)
             iters[active] = it
             conv = (err <= tol) & (it >= min_iter)
+            passed = np.where(active, conv, passed)
             active &= ~conv
             if not active.any():
                 break
+        self.last_converged = passed
         return V, iters
 
     def pu(self, V):
@@ -677,6 +690,7 @@ class BatchedPF:
         self.shape = load_loadshape()
         self.tol = tol
         self.semantics = semantics
+        self.last_iters = self.last_converged = None
 
     def base_loads(self, current_time):
         """opendss.py:106-108 for the model-1 loads; the others keep the DSS file's
@@ -710,8 +724,11 @@ class BatchedPF:
                     arr[:, names.index(name)] = arr[:, names.index(name)] + np.asarray(v, float)
         if self.semantics == "opendss":
             V, it = self.feeder.snap_opendss(kw, kvar, self.feeder.base_kw, self.feeder.base_kvar)
+            # (K,) bool: the last iteration passed OpenDSS's test (False: stopped by the cap)
+            self.last_converged = self.feeder.last_converged
         else:
             V, it = self.feeder.solve(kw, kvar, tol=self.tol)
+            self.last_converged = None
         self.last_iters = it
         return self.feeder.pu(V)
 

@@ -2597,9 +2597,14 @@ __global__ void __launch_bounds__(kBlock) k_pf_solve_od(PFArgs a, ODArgs o, pgw_
   const bool rows_lds = od_rows_lds<M>(a.n_out);     // (uniform)
   // extrema only with row records covering every candidate row (and row 0):
   // a block the table serves entirely reads the row records' headers and
-  // quartics alone -- no currents, no node-0 or row DPP groups, no row staging
+  // quartics alone -- no currents, no node-0 or row DPP groups, no row staging.
+  // Every candidate row needs a record to read there, a row-record slot or the
+  // node record: a row set that leaves one out (built for another node-record
+  // setting than these tables') takes the rows from the currents instead.
+  const uint64_t q_have = o.resp_q_rows | (o.resp_v_row > 0 ? 1ull << o.resp_v_row : 0ull) | 1ull;
   const bool qfast = table && v_out == nullptr && o.resp_q && rows_lds && o.resp_rows != 0 &&
-                     (od_q_slot(o, 0) >= 0 || o.resp_v_row == 0);        // (uniform)
+                     (od_q_slot(o, 0) >= 0 || o.resp_v_row == 0) &&
+                     (o.resp_rows & ~q_have) == 0ull;                    // (uniform)
   double rv[kOdRowQ];
   PFSolver<M, true, false> S;
   // the solve's operands (the block, the output rows) go out first -- in

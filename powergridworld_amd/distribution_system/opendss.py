@@ -363,6 +363,7 @@ class OpenDSSSolver(PowerFlowSolver):
         self.od_row_records = True           # pgw_pf_od.resp_q (False: the rows from the currents, for A/Bs)
         self._od_qrec = None                 # row records [table row, record, OD_QSTRIDE]
         self._od_qinfo = {}                  # (table row, configuration) -> (row bits, k) or None
+        self._od_qflags = {}                 # ... -> (od_node_records, od_record_rows) it was built with
         self.od_resp_stats, self.od_resp_brackets = {}, {}
         self._od_index = {}
         self._od_keep = {}
@@ -527,10 +528,20 @@ class OpenDSSSolver(PowerFlowSolver):
         fp64.  Written into the row's slice of the row-record buffer with the
         response records' headers copied bitwise.  Returns (row bits, k) or None
         (no mask, more than OD_QROWS rows, no response table).  Cached per
-        (row, configuration)."""
+        (row, configuration) and rebuilt when od_node_records or od_record_rows
+        changed since: the listed rows leave out the node records' row only
+        while that row has a node record to read."""
         key = (idx, self._cfg_version)
-        if key in self._od_qinfo:
+        flags = (bool(self.od_node_records), bool(self.od_record_rows))
+        if key in self._od_qinfo and self._od_qflags.get(key) == flags:
             return self._od_qinfo[key]
+        if key in self._od_qinfo:
+            # the row's records are rewritten in place: tables handed out with
+            # the old row set must not be used again
+            self._tables_cache.clear()
+            self._od_keep.clear()
+            self.tables_version += 1
+        self._od_qflags[key] = flags
         info = None
         mask = self._od_row_mask(idx)
         names = list(self.output_names)

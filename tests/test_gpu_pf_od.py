@@ -371,14 +371,15 @@ def _unfit(solver, every):
 def test_od_split_step_bit_identical(n, every, steps):
     """The fused C4 step with the agents, the table lookup and the snap solve
     of the envs the table leaves in one launch (k_coord_step_od: the lookup
-    wave's od_wave_solve, one env at a time; with PGW_STEP_LIST=1 the list form,
-    those envs listed for k_coord_pf_od_list) against the two-kernel step
+    wave's od_wave_solve, one env at a time) against the two-kernel step
     (k_coord_agents_std + k_coord_pf_od): every output bit for bit -- with the
     table serving (every = 0), with a third of the records forced unfit and with
     all of them (every env solved by the wave solve; at 66 000 envs, 1 032
     blocks of 64 solves each) -- and the all-unfit case equal to the step
     without a table (od_table=False).  od_count counts the envs left to the
-    solve in both forms."""
+    solve.  (The list form -- PGW_STEP_LIST=1, read when the library loads:
+    those envs listed for k_coord_pf_od_list -- does not run here; a child
+    process of tests/test_gpu_pf_offgrid.py runs it, tests/_step_list_child.py.)"""
     from powergridworld_amd.scenarios.coordinated import CoordinatedMultiBuildingControlEnv, make_c4_config
     envs = [CoordinatedMultiBuildingControlEnv(**make_c4_config(), num_envs=n, device=DEV, fused=True)
             for _ in range(3)]
