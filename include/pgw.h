@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define PGW_ABI_VERSION 31
+#define PGW_ABI_VERSION 32
 
 #define PGW_OK 0
 #define PGW_ERR_ARG (-1)
@@ -42,10 +42,10 @@ const char* pgw_last_error(void);
  * reduce_args, pf_params, pf_tables, feeder_elem, coord_params, coord_buffers,
  * coord_step_info, pred_meta, hs_params, hs_step_info, hs_buffers,
  * mc_step_args, matf, coord_buffers_f32, ma_step_args, pfg_elem, pfg_params,
- * pfg_tables, reg_params, mc_step_dyn, pf_od, mc_step_args_f32 -- lets a
- * binding verify its layouts.  Writes min(n, PGW_N_STRUCT_SIZES) values,
+ * pfg_tables, reg_params, mc_step_dyn, pf_od, mc_step_args_f32,
+ * od_certify_model -- lets a binding verify its layouts.  Writes min(n, PGW_N_STRUCT_SIZES) values,
  * returns PGW_N_STRUCT_SIZES. */
-#define PGW_N_STRUCT_SIZES 30
+#define PGW_N_STRUCT_SIZES 31
 int32_t pgw_struct_sizes(int64_t* out, int32_t n);
 
 /* A [n_envs x dim] fp64 matrix in device memory: element (e, j) at
@@ -515,6 +515,33 @@ int64_t pgw_pf_od_probe_args_size(int32_t n_hours);
 int32_t pgw_pf_od_probe(const pgw_pf_params* p_hours, int32_t n_hours, const pgw_pf_tables* t,
                         const double* start_h, int32_t lanes_per_hour, int64_t n, const double* P,
                         double* J_out, uint64_t* sig_out, int32_t* it_out, void* args_buf, void* stream);
+
+/* Response-table certificate (distribution_system/od_certify.py certify(),
+ * one kernel per refinement level): the snap solve's model with one
+ * controllable slot, per hour row h: u_1 = u1b[h] + P u1P, iteration 1's
+ * currents J0[h] + P jP, then J = (s g(|u|^2) - y0) u with s = s0[h] + P fr,
+ * u_next = u0 + W J, every node V = V0 + G J.  Device pointers; complex arrays
+ * as (re, im) pairs: u1b, J0, s0 [n_hours][m]; u1P, jP, y0, u0 [m]; fr [m]
+ * real; W [m][m] and G [n_nodes][m] row-major with their element-wise
+ * magnitudes Wa, Ga (real); V0 [n_nodes].  lo2 < mn2 < mx2: the squared band
+ * thresholds; a decision is certain when its margin clears the threshold by
+ * delta_band (bands) or delta_stop (the stopping test against tol). */
+typedef struct pgw_od_certify_model {
+  const double *u1b, *u1P, *J0, *jP, *s0, *fr, *y0, *u0, *W, *Wa, *G, *Ga, *V0;
+  double lo2, mn2, mx2, tol, delta_band, delta_stop;
+  int32_t m, n_nodes, n_hours, min_iter, max_iter, pad_;
+} pgw_od_certify_model;
+#define PGW_OD_CERTIFY_MAX_NODES 42 /* three doubles per node and lane in 64 KiB of LDS */
+
+/* Certifies k intervals [lo[i], hi[i]] (kW) of hour rows h[i] in one launch,
+ * one lane per interval, the whole iteration loop on the device: ok[i] = 1
+ * when every band and stopping decision of the snap solve is the same at every
+ * P of the interval; ret[i] the iteration count (negative: stopped by max_iter
+ * or by an uncertain decision); sig[i] the signature of those decisions
+ * (pgw_pf_od_probe's hash).  m must be 14, 2 <= max_iter, h[i] in [0, n_hours)
+ * (a row outside it gives ok = 0, ret = 0). */
+int32_t pgw_pf_od_certify(const pgw_od_certify_model* model, int64_t k, const int32_t* h, const double* lo,
+                          const double* hi, int32_t* ok, int32_t* ret, uint64_t* sig, void* stream);
 
 /* Pieces -> response records (device).  Piece i: fit points a < mid < b whose
  * currents are J[ia], J[im], J[ib] (m complex each; idx3[3 i ..]), its

@@ -12,7 +12,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # PGW_LIB_PATH: another build of the same ABI (same-box A/B measurements only)
 LIB_PATH = os.environ.get("PGW_LIB_PATH") or os.path.join(_HERE, "libpgw.so")
-ABI_VERSION = 31
+ABI_VERSION = 32
 
 f64, i32, i64, u64, vp = C.c_double, C.c_int32, C.c_int64, C.c_uint64, C.c_void_p
 P = C.POINTER
@@ -296,6 +296,15 @@ class HSBuffers(C.Structure):
                 ("pv_power_last", vp), ("min_voltage", vp)]
 
 
+class ODCertifyModel(C.Structure):
+    """pgw_od_certify_model: the snap solve's model for pgw_pf_od_certify (od_certify.SnapModel)."""
+    _fields_ = [(k, vp) for k in ("u1b", "u1P", "J0", "jP", "s0", "fr", "y0", "u0", "W", "Wa", "G", "Ga", "V0")] + \
+               [(k, f64) for k in ("lo2", "mn2", "mx2", "tol", "delta_band", "delta_stop")] + \
+               [(k, i32) for k in ("m", "n_nodes", "n_hours", "min_iter", "max_iter", "pad_")]
+
+
+OD_CERTIFY_MAX_NODES = 42
+
 PGW_ELEM_LINE, PGW_ELEM_XFMR, PGW_ELEM_VSOURCE, PGW_ELEM_SHUNT, PGW_ELEM_XFMR_N = 1, 2, 3, 4, 5
 
 _SIGS = {
@@ -303,6 +312,7 @@ _SIGS = {
     "pgw_struct_sizes": (i32, [P(i64), i32]),
     "pgw_pf_od_probe_args_size": (i64, [i32]),
     "pgw_pf_od_probe": (i32, [P(PFParams), i32, P(PFTables), vp, i32, i64, vp, vp, vp, vp, vp, vp]),
+    "pgw_pf_od_certify": (i32, [P(ODCertifyModel), i64, vp, vp, vp, vp, vp, vp, vp]),
     "pgw_pf_od_resp_fit": (i32, [i32, i64, vp, vp, vp, vp, vp, vp, vp]),
     "pgw_pf_od_resp_check": (i32, [i32, i64, vp, vp, vp, vp, vp, vp, vp]),
     "pgw_last_error": (C.c_char_p, []),
@@ -371,7 +381,8 @@ EXPORTED = sorted(_SIGS)
 STRUCTS = [Mat, BatteryParams, PVParams, BuildingParams, BuildingExo, BuildingExt, EVParams,
            EVStepInfo, ReduceArgs, PFParams, PFTables, FeederElem, CoordParams, CoordBuffers,
            CoordStepInfo, PredMeta, HSParams, HSStepInfo, HSBuffers, MCStepArgs, Matf, CoordBuffersF32,
-           MAStepArgs, PFGElem, PFGParams, PFGTables, RegParams, MCStepDyn, PFOD, MCStepArgsF32]
+           MAStepArgs, PFGElem, PFGParams, PFGTables, RegParams, MCStepDyn, PFOD, MCStepArgsF32,
+           ODCertifyModel]
 
 _lib = None
 

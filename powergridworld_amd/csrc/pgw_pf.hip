@@ -35,6 +35,7 @@
 #include <vector>
 
 #include "pgw_common.h"
+#include "pgw_od_certify.h"
 
 // pgw_debug_pf_trace set: k_coord_pf_od launches its trace instantiation
 static std::atomic<bool> g_pf_trace_on{false};
@@ -2768,6 +2769,34 @@ __global__ void __launch_bounds__(kBlock) k_pf_od_probe(const PFArgs* __restrict
   it_out[e] = it;
 }
 
+// Response-table certificate (pgw_pf_od_certify): one interval per lane, the
+// whole iteration loop of od_certify.certify() in od_certify_lane.  A lane keeps
+// its iterate's and currents' models in registers (2 x 5 M doubles) and the
+// previous iteration's node magnitude models in LDS (3 n_nodes doubles per
+// lane, lane-minor: no bank conflicts); the matrices are read at uniform
+// addresses.  One wave per block: a few thousand intervals spread over the CUs,
+// and no lane waits for another (no barrier, no cross-lane operation).
+constexpr int kCertBlock = 64;
+template <int M>
+__global__ void __launch_bounds__(kCertBlock) k_pf_od_certify(pgw_od_certify_model a, int64_t K,
+                                                              const int32_t* __restrict__ h,
+                                                              const double* __restrict__ lo,
+                                                              const double* __restrict__ hi,
+                                                              int32_t* __restrict__ ok, int32_t* __restrict__ ret,
+                                                              uint64_t* __restrict__ sig) {
+  extern __shared__ double cert_prev[];                 // [3 n_nodes][kCertBlock]
+  const int64_t e = (int64_t)blockIdx.x * kCertBlock + threadIdx.x;
+  if (e >= K) return;
+  const int row = h[e];
+  if (row < 0 || row >= a.n_hours) {
+    ok[e] = 0;
+    ret[e] = 0;
+    sig[e] = 0;
+    return;
+  }
+  od_certify_lane<M>(a, row, lo[e], hi[e], cert_prev + threadIdx.x, kCertBlock, ok + e, ret + e, sig + e);
+}
+
 // Pieces -> records (pgw_pf_od_resp_fit), one thread per piece.
 __global__ void __launch_bounds__(kBlock) k_pf_od_resp_fit(int32_t m, int64_t np, const double2* __restrict__ J,
                                                            const int32_t* __restrict__ idx3,
@@ -3332,6 +3361,26 @@ int32_t pgw_pf_od_probe(const pgw_pf_params* p_hours, int32_t n_hours, const pgw
                      reinterpret_cast<const PFArgs*>(args_buf), make_od_args(*t->od, p_hours[0].max_iter), *t,
                      start_h, lanes_per_hour, n, P, reinterpret_cast<double2*>(J_out), sig_out, it_out);
   return check_launch("k_pf_od_probe");
+}
+
+int32_t pgw_pf_od_certify(const pgw_od_certify_model* model, int64_t k, const int32_t* h, const double* lo,
+                          const double* hi, int32_t* ok, int32_t* ret, uint64_t* sig, void* stream) {
+  PGW_REQUIRE(model && k >= 0, "pgw_pf_od_certify: null model / negative k");
+  const pgw_od_certify_model& a = *model;
+  PGW_REQUIRE(a.m == 14 && a.n_nodes >= 1 && a.n_nodes <= PGW_OD_CERTIFY_MAX_NODES && a.n_hours >= 1 &&
+              a.max_iter >= 2,
+              "pgw_pf_od_certify: m %d (14), n_nodes %d (1..%d), n_hours %d, max_iter %d (>= 2)", a.m, a.n_nodes,
+              PGW_OD_CERTIFY_MAX_NODES, a.n_hours, a.max_iter);
+  PGW_REQUIRE(a.u1b && a.u1P && a.J0 && a.jP && a.s0 && a.fr && a.y0 && a.u0 && a.W && a.Wa && a.G && a.Ga && a.V0,
+              "pgw_pf_od_certify: null model array");
+  if (k == 0) return PGW_OK;
+  PGW_REQUIRE(h && lo && hi && ok && ret && sig, "pgw_pf_od_certify: null argument");
+  const int64_t blocks = (k + kCertBlock - 1) / kCertBlock;
+  PGW_REQUIRE(blocks <= 0x7fffffffll, "pgw_pf_od_certify: %lld intervals", (long long)k);
+  const size_t lds = sizeof(double) * 3 * (size_t)a.n_nodes * kCertBlock;
+  hipLaunchKernelGGL(k_pf_od_certify<14>, dim3((unsigned)blocks), dim3(kCertBlock), lds, (hipStream_t)stream, a, k,
+                     h, lo, hi, ok, ret, sig);
+  return check_launch("k_pf_od_certify");
 }
 
 int32_t pgw_pf_od_resp_fit(int32_t m, int64_t n_pieces, const double* J, const int32_t* idx3,

@@ -360,6 +360,7 @@ class OpenDSSSolver(PowerFlowSolver):
         self.od_row_masks = True             # pgw_pf_od.resp_rows (False: every row, for A/Bs and tests)
         self.od_record_rows = True           # row records' per-record candidate slots (False: every slot)
         self.od_certify = True               # certify every piece (od_certify; False: probes only, for A/Bs)
+        self.od_certify_native = True        # the certificate in k_pf_od_certify (False: the torch program, for A/Bs)
         self.od_row_records = True           # pgw_pf_od.resp_q (False: the rows from the currents, for A/Bs)
         self._od_qrec = None                 # row records [table row, record, OD_QSTRIDE]
         self._od_qinfo = {}                  # (table row, configuration) -> (row bits, k) or None
@@ -786,6 +787,7 @@ class OpenDSSSolver(PowerFlowSolver):
         if self.od_certify and len(cand):
             from powergridworld_amd.distribution_system.od_certify import SnapModel, certify_pieces
             model = SnapModel.from_solver(self, list(range(idx0, idx0 + H)), hours)
+            model.native = bool(self.od_certify_native)
             c_lo, c_hi, c_kw = certify_pieces(model, pq_[cand], pa[cand], pb[cand], pit[cand], psig[cand],
                                               min_width=self.OD_RESP_MIN_WIDTH)
             none = c_lo > c_hi
