@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define PGW_ABI_VERSION 32
+#define PGW_ABI_VERSION 33
 
 #define PGW_OK 0
 #define PGW_ERR_ARG (-1)
@@ -43,9 +43,9 @@ const char* pgw_last_error(void);
  * coord_step_info, pred_meta, hs_params, hs_step_info, hs_buffers,
  * mc_step_args, matf, coord_buffers_f32, ma_step_args, pfg_elem, pfg_params,
  * pfg_tables, reg_params, mc_step_dyn, pf_od, mc_step_args_f32,
- * od_certify_model -- lets a binding verify its layouts.  Writes min(n, PGW_N_STRUCT_SIZES) values,
- * returns PGW_N_STRUCT_SIZES. */
-#define PGW_N_STRUCT_SIZES 31
+ * od_certify_model, ma_step_args_f32 -- lets a binding verify its layouts.  Writes
+ * min(n, PGW_N_STRUCT_SIZES) values, returns PGW_N_STRUCT_SIZES. */
+#define PGW_N_STRUCT_SIZES 32
 int32_t pgw_struct_sizes(int64_t* out, int32_t n);
 
 /* A [n_envs x dim] fp64 matrix in device memory: element (e, j) at
@@ -920,6 +920,14 @@ typedef struct pgw_coord_buffers_f32 {
   float* v_out;
   float* vv;
   int32_t* iters;
+  /* as pgw_coord_buffers' (null: the two-kernel step).  The one-launch fp32
+   * step (k_coord_step_od_f32) holds an env pair per lane: it needs an even n,
+   * env-minor action / obs views with even strides and 8-byte aligned buffers;
+   * otherwise -- or with PGW_STEP_LIST=1 / PGW_STEP_WT=1 -- the step runs the
+   * two kernels and zeroes the next step's od_count itself. */
+  int32_t* od_list;
+  int32_t* od_count;
+  int32_t od_parity, pad_;
 } pgw_coord_buffers_f32;
 
 /* The same coordinated step with the general power flow (pgw_pf_solve_general:
@@ -1129,6 +1137,57 @@ typedef struct pgw_ma_step_args {
  * v_out may be NULL when pft carries v_min_out / v_max_out (extrema only). */
 int32_t pgw_ma_step(const pgw_ma_step_args* a, const pgw_pf_params* pf, const pgw_pf_tables* pft,
                     int64_t n, double* v_out, int32_t* iters, void* stream);
+
+/* fp32 storage variant: the same fields and layout, every per-env
+ * buffer of the agents (state, obs, actions, real powers, rewards) fp32.  The
+ * rounding contract is pgw_mc_agent_step_f32's: fp64 arithmetic, each value
+ * rounded once at its store; a MultiComponentEnv agent's real_power / reward
+ * are the fp64 in-order sums of its components' STORED values (widened),
+ * rounded at their store; the band reward is the fp64 expression on the fp64
+ * min_voltage, rounded at its store.  bus_p stays fp64: 0 + a0 + a1 ... over
+ * the agents' stored real powers, widened -- and with it the power-flow half
+ * (voltages, extrema, iteration counts), which is pgw_ma_step's.  ev_endp,
+ * ev_charging and the min_voltage inputs keep their types. */
+typedef struct pgw_ma_step_args_f32 {
+  int32_t n_comp, pad_;
+  pgw_mc_component_f32 comp[PGW_MA_MAX_SLOTS];
+  pgw_building_params bld;
+  pgw_building_exo bld_ex_t, bld_ex_next;
+  pgw_building_ext bld_ext;
+  float* bld_x;
+  float* bld_reward_state;
+  pgw_pv_params pv;
+  double pv_pmax;
+  const double* pv_min_voltage;
+  pgw_battery_params bat;
+  float* bat_soc;
+  pgw_ev_params ev;
+  pgw_ev_step_info ev_step;
+  const double* ev_endp;
+  float* ev_req;
+  uint64_t* ev_charging;
+  float* ev_reward;
+  pgw_pv_params pv2;
+  double pv2_pmax;
+  const double* pv2_min_voltage;
+  int32_t slot_agent[PGW_MA_MAX_SLOTS];
+  int32_t slot_pv2[PGW_MA_MAX_SLOTS];
+  float* slot_reward[PGW_MA_MAX_SLOTS];
+  double band_lo, band_hi, band_scale;
+  int32_t n_agents, n_bus;
+  int32_t agent_first[PGW_MAX_AGENTS], agent_count[PGW_MAX_AGENTS];
+  int32_t agent_bus[PGW_MAX_AGENTS], agent_sum[PGW_MAX_AGENTS];
+  float* agent_real_power[PGW_MAX_AGENTS];
+  float* agent_reward[PGW_MAX_AGENTS];
+  double* bus_p;
+  int32_t n_waves, pad2_;
+  int32_t wave_first[PGW_MA_MAX_SLOTS], wave_count[PGW_MA_MAX_SLOTS];
+  int32_t wave_slot[PGW_MA_MAX_SLOTS];
+} pgw_ma_step_args_f32;
+
+int32_t pgw_ma_step_f32(const pgw_ma_step_args_f32* a, const pgw_pf_params* pf,
+                        const pgw_pf_tables* pft, int64_t n, double* v_out, int32_t* iters,
+                        void* stream);
 
 /* ------------------------------------------------------------------------
  * Home-Steward house: HSMultiComponentEnv.reset/step

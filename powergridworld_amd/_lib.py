@@ -12,7 +12,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # PGW_LIB_PATH: another build of the same ABI (same-box A/B measurements only)
 LIB_PATH = os.environ.get("PGW_LIB_PATH") or os.path.join(_HERE, "libpgw.so")
-ABI_VERSION = 32
+ABI_VERSION = 33
 
 f64, i32, i64, u64, vp = C.c_double, C.c_int32, C.c_int64, C.c_uint64, C.c_void_p
 P = C.POINTER
@@ -203,7 +203,8 @@ class CoordBuffers(C.Structure):
 class CoordBuffersF32(C.Structure):
     _fields_ = [("action", Matf), ("act_stride_agent", i64), ("obs", Matf), ("obs_stride_agent", i64),
                 ("x", vp), ("soc", vp), ("reward", vp), ("agent_power", vp), ("v_out", vp),
-                ("vv", vp), ("iters", vp)]
+                ("vv", vp), ("iters", vp), ("od_list", vp), ("od_count", vp), ("od_parity", i32),
+                ("pad_", i32)]
 
 
 class CoordStepInfo(C.Structure):
@@ -267,6 +268,12 @@ class MAStepArgs(C.Structure):
                 ("agent_real_power", vp * MAX_AGENTS), ("agent_reward", vp * MAX_AGENTS), ("bus_p", vp),
                 ("n_waves", i32), ("pad2_", i32), ("wave_first", i32 * MA_MAX_SLOTS),
                 ("wave_count", i32 * MA_MAX_SLOTS), ("wave_slot", i32 * MA_MAX_SLOTS)]
+
+
+class MAStepArgsF32(C.Structure):
+    """pgw_ma_step_args_f32: pgw_ma_step_args with fp32 per-env buffers (the same
+    field names and layout)."""
+    _fields_ = [(nm, MCComponentF32 * MA_MAX_SLOTS) if nm == "comp" else (nm, tp) for nm, tp in MAStepArgs._fields_]
 
 
 class HSParams(C.Structure):
@@ -374,6 +381,7 @@ _SIGS = {
     "pgw_graph_destroy": (i32, [vp]),
     "pgw_hs_step": (i32, [P(HSParams), P(HSStepInfo), i64, HSBuffers, vp]),
     "pgw_ma_step": (i32, [P(MAStepArgs), P(PFParams), P(PFTables), i64, vp, vp, vp]),
+    "pgw_ma_step_f32": (i32, [P(MAStepArgsF32), P(PFParams), P(PFTables), i64, vp, vp, vp]),
 }
 
 EXPORTED = sorted(_SIGS)
@@ -382,7 +390,7 @@ STRUCTS = [Mat, BatteryParams, PVParams, BuildingParams, BuildingExo, BuildingEx
            EVStepInfo, ReduceArgs, PFParams, PFTables, FeederElem, CoordParams, CoordBuffers,
            CoordStepInfo, PredMeta, HSParams, HSStepInfo, HSBuffers, MCStepArgs, Matf, CoordBuffersF32,
            MAStepArgs, PFGElem, PFGParams, PFGTables, RegParams, MCStepDyn, PFOD, MCStepArgsF32,
-           ODCertifyModel]
+           ODCertifyModel, MAStepArgsF32]
 
 _lib = None
 

@@ -1034,14 +1034,15 @@ __global__ void __launch_bounds__(64 * (4 + kEvGroups - 1)) k_mc_step(Args a_, B
 // register count did not all fit at once.
 // The agents' and buses' part of pgw_ma_step_args (n_agents .. bus_p), as laid
 // out there: copied whole into LDS for the sums.
-struct MaSums {
+template <class S> struct MaSumsT {
   int32_t n_agents, n_bus;
   int32_t first[PGW_MAX_AGENTS], count[PGW_MAX_AGENTS];
   int32_t bus[PGW_MAX_AGENTS], sum[PGW_MAX_AGENTS];
-  double* rp[PGW_MAX_AGENTS];
-  double* rew[PGW_MAX_AGENTS];
+  S* rp[PGW_MAX_AGENTS];
+  S* rew[PGW_MAX_AGENTS];
   double* bus_p;
 };
+using MaSums = MaSumsT<double>;
 static_assert(offsetof(pgw_ma_step_args, n_waves) - offsetof(pgw_ma_step_args, n_agents) == sizeof(MaSums) &&
               offsetof(pgw_ma_step_args, n_agents) % 8 == 0 && sizeof(MaSums) % 8 == 0 && sizeof(MaSums) / 8 <= 64,
               "MaSums mirrors pgw_ma_step_args");
@@ -1050,25 +1051,43 @@ static_assert(offsetof(pgw_ma_step_args, agent_first) - offsetof(pgw_ma_step_arg
               offsetof(pgw_ma_step_args, agent_real_power) - offsetof(pgw_ma_step_args, n_agents) == offsetof(MaSums, rp) &&
               offsetof(pgw_ma_step_args, bus_p) - offsetof(pgw_ma_step_args, n_agents) == offsetof(MaSums, bus_p),
               "MaSums field offsets");
+// Args: pgw_ma_step_args (fp64 storage) or pgw_ma_step_args_f32 (fp32 storage,
+// the same layout: MaSumsT<float> mirrors it as MaSums does the fp64 struct).
+template <> struct McStore<pgw_ma_step_args_f32> {
+  using S = float;
+  using Mt = pgw_matf;
+};
+static_assert(sizeof(pgw_ma_step_args_f32) == sizeof(pgw_ma_step_args) && sizeof(MaSumsT<float>) == sizeof(MaSums) &&
+              offsetof(pgw_ma_step_args_f32, n_agents) == offsetof(pgw_ma_step_args, n_agents) &&
+              offsetof(pgw_ma_step_args_f32, bus_p) == offsetof(pgw_ma_step_args, bus_p) &&
+              offsetof(pgw_ma_step_args_f32, wave_slot) == offsetof(pgw_ma_step_args, wave_slot),
+              "pgw_ma_step_args_f32 layout");
 
 // (3 waves per SIMD at least: the heterogeneous scenario's 1 024 three-wave
 // blocks then all fit at once, 4 per CU; at 2 they ran in two rounds)
-template <bool STD, bool TR = false>
-__global__ void __launch_bounds__(64 * PGW_MA_MAX_SLOTS) __attribute__((amdgpu_waves_per_eu(3))) k_ma_step(pgw_ma_step_args a_, BldDerived d,
+//
+// fp32 storage (Args = pgw_ma_step_args_f32): fp64 arithmetic, each value
+// rounded once at its store; the sums below add the STORED values widened (what
+// pgw_agent_reduce would read back), so s_rp / s_rew hold those.
+template <bool STD, bool TR = false, class Args = pgw_ma_step_args>
+__global__ void __launch_bounds__(64 * PGW_MA_MAX_SLOTS) __attribute__((amdgpu_waves_per_eu(3))) k_ma_step(Args a_, BldDerived d,
                                                                    int64_t n) {
-  const pgw_ma_step_args& a = PGW_KERNARG0(pgw_ma_step_args);
+  using S = typename McStore<Args>::S;
+  using Mt = typename McStore<Args>::Mt;
+  using Comp = typename std::remove_reference<decltype(a_.comp[0])>::type;
+  const Args& a = PGW_KERNARG0(Args);
   long long* const tr = TR ? g_mc_trace : nullptr;
   mc_trace<TR>(tr, 0);
   __shared__ double s_rp[PGW_MA_MAX_SLOTS][64], s_rew[PGW_MA_MAX_SLOTS][64];
   __shared__ pgw_building_params s_bp;                // the building wave's parameters (bld_stage_wave)
   __shared__ BldDerived s_bd;
-  __shared__ MaSums s_sums;
+  __shared__ MaSumsT<S> s_sums;
   const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   // the sums' plan (agents' slots, buses, output pointers), read by wave 0
   // after the barrier: staged here by the block's last wave (not the
   // building's), so the tail is LDS reads, not ~40 waited scalar loads
   if (wv == (int)(blockDim.x >> 6) - 1) {
-    constexpr int kW = (int)(sizeof(MaSums) / 8);
+    constexpr int kW = (int)(sizeof(MaSumsT<S>) / 8);
     const int l = (int)(threadIdx.x & 63);
     if (l < kW) reinterpret_cast<uint64_t*>(&s_sums)[l] = reinterpret_cast<const uint64_t*>(&a.n_agents)[l];
   }
@@ -1081,24 +1100,24 @@ __global__ void __launch_bounds__(64 * PGW_MA_MAX_SLOTS) __attribute__((amdgpu_w
   const int c0 = a.wave_slot[a.wave_first[wv]];
   const int kind0 = a.comp[c0].kind;
   if (STD && kind0 == PGW_MC_BUILDING) {           // (uniform) every lane stages: bld_wave_std
-    const pgw_mc_component& C = a.comp[c0];
-    const RpRew r = bld_wave_std<double, pgw_mat, TR>(a.bld, d, s_bp, s_bd, a.bld_ex_t, a.bld_ex_next, n, e,
-                                                      C.action, a.bld_x, C.real_power, a.bld_reward_state, C.obs);
+    const Comp& C = a.comp[c0];
+    const RpRew r = bld_wave_std<S, Mt, TR>(a.bld, d, s_bp, s_bd, a.bld_ex_t, a.bld_ex_next, n, e, C.action,
+                                            a.bld_x, C.real_power, a.bld_reward_state, C.obs);
     if (e < n) {
       s_rp[c0][lane] = r.rp;
       s_rew[c0][lane] = r.rew;                      // the fresh reward (MC semantics)
     }
   } else if (e < n) {
     if (kind0 == PGW_MC_BUILDING) {
-      const pgw_mc_component& C = a.comp[c0];
+      const Comp& C = a.comp[c0];
       double fresh = 0.0;                             // the fresh reward (MC semantics)
-      s_rp[c0][lane] = building_step_env<STD, double, pgw_mat, TR>(a.bld, d, a.bld_ex_t, a.bld_ex_next, n, e,
-                                                                   C.action, a.bld_x, C.real_power, nullptr,
-                                                                   a.bld_reward_state, 0, a.bld_ext, C.obs,
-                                                                   &fresh);
+      s_rp[c0][lane] = (double)(S)building_step_env<STD, S, Mt, TR>(a.bld, d, a.bld_ex_t, a.bld_ex_next, n, e,
+                                                                    C.action, a.bld_x, C.real_power, nullptr,
+                                                                    a.bld_reward_state, 0, a.bld_ext, C.obs,
+                                                                    &fresh);
       s_rew[c0][lane] = fresh;
     } else if (kind0 == PGW_MC_EV) {
-      const pgw_mc_component& C = a.comp[c0];
+      const Comp& C = a.comp[c0];
       const RpRew r = ev_step_env(a.ev, a.ev_step, n, e, C.action, a.ev_endp, a.ev_req, a.ev_charging, C.obs,
                                   C.real_power, a.ev_reward);
       s_rp[c0][lane] = r.rp;
@@ -1114,7 +1133,7 @@ __global__ void __launch_bounds__(64 * PGW_MA_MAX_SLOTS) __attribute__((amdgpu_w
       for (int i = 0; i < PGW_MA_MAX_SLOTS; ++i) {
         if (i >= cnt) break;
         const int w = a.wave_slot[first + i];
-        const pgw_mc_component& C = a.comp[w];
+        const Comp& C = a.comp[w];
         act_v[i] = C.action.ptr ? ld(C.action, e, 0) : 0.0;
         if (C.kind == PGW_MC_PV) {
           const bool two = a.slot_pv2[w] != 0;
@@ -1128,7 +1147,7 @@ __global__ void __launch_bounds__(64 * PGW_MA_MAX_SLOTS) __attribute__((amdgpu_w
       for (int i = 0; i < PGW_MA_MAX_SLOTS; ++i) {
         if (i >= cnt) break;
         const int w = a.wave_slot[first + i];
-        const pgw_mc_component& C = a.comp[w];
+        const Comp& C = a.comp[w];
         double rp, rew = 0.0;
         if (C.kind == PGW_MC_PV) {                    // pv_step_env on the loaded values
           const bool two = a.slot_pv2[w] != 0;
@@ -1142,18 +1161,20 @@ __global__ void __launch_bounds__(64 * PGW_MA_MAX_SLOTS) __attribute__((amdgpu_w
             const double l = x - a.band_lo, u = a.band_hi - x;
             const double viol = ((l < 0.0) ? l : 0.0) + ((u < 0.0) ? u : 0.0);
             const double y = a.band_scale * viol;
-            rew = -(y * y);
-            a.slot_reward[w][e] = rew;
+            const S rw = (S)(-(y * y));
+            a.slot_reward[w][e] = rw;
+            rew = (double)rw;
           }
         } else {                                      // battery_step_env on the loaded values
           double soc = st_v[i];
           const double power = battery_step(a.bat, act_v[i], soc);
-          a.bat_soc[e] = soc;
+          a.bat_soc[e] = (S)soc;
           st(C.obs, e, 0, battery_obs(a.bat, soc));
           rp = -power;
         }
-        C.real_power[e] = rp;
-        s_rp[w][lane] = rp;
+        const S rps = (S)rp;
+        C.real_power[e] = rps;
+        s_rp[w][lane] = (double)rps;
         s_rew[w][lane] = rew;
       }
     }
@@ -1162,7 +1183,7 @@ __global__ void __launch_bounds__(64 * PGW_MA_MAX_SLOTS) __attribute__((amdgpu_w
   __syncthreads();
   mc_trace<TR>(tr, 5);
   if (wv != 0 || e >= n) return;
-  const MaSums& m = s_sums;
+  const MaSumsT<S>& m = s_sums;
   double ap[PGW_MAX_AGENTS];
 #pragma unroll
   for (int g = 0; g < PGW_MAX_AGENTS; ++g) {     // (constant indices: ap stays in registers)
@@ -1175,9 +1196,10 @@ __global__ void __launch_bounds__(64 * PGW_MA_MAX_SLOTS) __attribute__((amdgpu_w
         rp_sum = rp_sum + s_rp[c][lane];
         rew_sum = rew_sum + s_rew[c][lane];
       }
-      m.rp[g][e] = rp_sum;
-      m.rew[g][e] = rew_sum;
-      ap[g] = rp_sum;
+      const S rps = (S)rp_sum;
+      m.rp[g][e] = rps;
+      m.rew[g][e] = (S)rew_sum;
+      ap[g] = (double)rps;
     } else {
       ap[g] = s_rp[c0][lane];
     }
@@ -1530,8 +1552,12 @@ int32_t pgw_mc_agent_step_f32(const pgw_mc_step_args_f32* a, int64_t n, void* st
   return mc_agent_step(a, n, stream);
 }
 
-int32_t pgw_ma_step(const pgw_ma_step_args* a, const pgw_pf_params* pf, const pgw_pf_tables* pft,
-                    int64_t n, double* v_out, int32_t* iters, void* stream) {
+}  // extern "C"
+
+// pgw_ma_step / pgw_ma_step_f32 (the messages name the former for both)
+template <class Args>
+static int32_t ma_step(const Args* a, const pgw_pf_params* pf, const pgw_pf_tables* pft, int64_t n,
+                       double* v_out, int32_t* iters, void* stream) {
   PGW_REQUIRE(a && n >= 0 && a->n_comp >= 1 && a->n_comp <= PGW_MA_MAX_SLOTS, "pgw_ma_step: bad args");
   PGW_REQUIRE(a->n_agents >= 1 && a->n_agents <= PGW_MAX_AGENTS, "pgw_ma_step: bad n_agents");
   PGW_REQUIRE(a->n_bus >= 0 && a->n_bus <= PGW_PF_MAX_CTRL && (a->n_bus == 0 || a->bus_p),
@@ -1569,7 +1595,7 @@ int32_t pgw_ma_step(const pgw_ma_step_args* a, const pgw_pf_params* pf, const pg
   // no building: the STD instantiation (its building branch never runs)
   bool std_bld = true;
   for (int c = 0; c < a->n_comp; ++c) {
-    const pgw_mc_component& C = a->comp[c];
+    const auto& C = a->comp[c];
     PGW_REQUIRE(C.kind >= 0 && C.kind <= 3, "pgw_ma_step: slot %d kind", c);
     PGW_REQUIRE(C.action.ptr && C.obs.ptr && C.real_power, "pgw_ma_step: slot %d buffers", c);
     if (C.kind == PGW_MC_PV) {
@@ -1603,15 +1629,27 @@ int32_t pgw_ma_step(const pgw_ma_step_args* a, const pgw_pf_params* pf, const pg
   const dim3 grid((unsigned)((n + 63) / 64)), block(64u * (unsigned)a->n_waves);
   hipStream_t st = (hipStream_t)stream;
   if (g_mc_trace_on.load())
-    std_bld ? launch_timed(PGW_T_MA_STEP, k_ma_step<true, true>, grid, block, st, *a, d, n)
-            : launch_timed(PGW_T_MA_STEP, k_ma_step<false, true>, grid, block, st, *a, d, n);
+    std_bld ? launch_timed(PGW_T_MA_STEP, (k_ma_step<true, true, Args>), grid, block, st, *a, d, n)
+            : launch_timed(PGW_T_MA_STEP, (k_ma_step<false, true, Args>), grid, block, st, *a, d, n);
   else if (std_bld)
-    launch_timed(PGW_T_MA_STEP, k_ma_step<true>, grid, block, st, *a, d, n);
+    launch_timed(PGW_T_MA_STEP, (k_ma_step<true, false, Args>), grid, block, st, *a, d, n);
   else
-    launch_timed(PGW_T_MA_STEP, k_ma_step<false>, grid, block, st, *a, d, n);
+    launch_timed(PGW_T_MA_STEP, (k_ma_step<false, false, Args>), grid, block, st, *a, d, n);
   const int32_t rc = check_launch("k_ma_step");
   if (rc || !pf) return rc;
   return pgw_pf_solve(pf, pft, n, a->n_bus ? a->bus_p : nullptr, nullptr, v_out, iters, stream);
+}
+
+extern "C" {
+
+int32_t pgw_ma_step(const pgw_ma_step_args* a, const pgw_pf_params* pf, const pgw_pf_tables* pft,
+                    int64_t n, double* v_out, int32_t* iters, void* stream) {
+  return ma_step(a, pf, pft, n, v_out, iters, stream);
+}
+
+int32_t pgw_ma_step_f32(const pgw_ma_step_args_f32* a, const pgw_pf_params* pf, const pgw_pf_tables* pft,
+                        int64_t n, double* v_out, int32_t* iters, void* stream) {
+  return ma_step(a, pf, pft, n, v_out, iters, stream);
 }
 
 int32_t pgw_agent_reduce(const pgw_reduce_args* a, int64_t n, double* real_power, double* reward,

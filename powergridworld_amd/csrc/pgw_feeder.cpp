@@ -285,7 +285,7 @@ int32_t pgw_struct_sizes(int64_t* out, int32_t n) {
       (int64_t)sizeof(pgw_pfg_params),     (int64_t)sizeof(pgw_pfg_tables),
       (int64_t)sizeof(pgw_reg_params),    (int64_t)sizeof(pgw_mc_step_dyn),
       (int64_t)sizeof(pgw_pf_od),         (int64_t)sizeof(pgw_mc_step_args_f32),
-      (int64_t)sizeof(pgw_od_certify_model)};
+      (int64_t)sizeof(pgw_od_certify_model), (int64_t)sizeof(pgw_ma_step_args_f32)};
   for (int i = 0; i < n && i < PGW_N_STRUCT_SIZES; ++i) out[i] = sz[i];
   return PGW_N_STRUCT_SIZES;
 }

@@ -2552,6 +2552,193 @@ __global__ void __launch_bounds__(64 * (PGW_MAX_AGENTS + 1)) __attribute__((amdg
   __syncthreads();
 }
 
+// The one-launch C4 step on fp32 buffers (pgw_coord_buffers_f32), the inline
+// form only (INL, plain stores).  Layout: env PAIRS -- a lane holds two
+// neighbouring envs and every global access is a 2-vector of 8 B a lane
+// (k_coord_agents_std_x2's accesses: with one fp32 env per lane the kernel
+// would issue the fp64 kernel's instruction count at half its bytes); a block
+// is 128 envs, again one wave per agent and the lookup wave, and
+// std_agent_compute<2, 1> / <2, 2> interleave the two envs' chains.  The
+// lookup wave serves two envs per lane: both cells and both node-record
+// gathers go out before the first chain compare (one L2 round trip for the
+// two), then the wave solve runs over both halves' left-over ballots.
+// Bit-identical to k_coord_agents_std_x2 + k_coord_pf_od<.., _f32>: whatever
+// the second kernel re-reads from fp32 storage is rounded to fp32 here before
+// its use -- the power published for the bus sum is (double)(float)power, the
+// raw reward is carried as a float and the final reward is the fp32 add
+// rw + (float)(-share); share and vv come from the fp64 |V| and are rounded
+// once at their stores.  Needs pairs_ok (an even n: a lane has both envs or
+// none) and 8-byte aligned v_out / vv / iters; two bodies behind the scalar
+// branch, each with its own barrier pair, as the fp64 kernel.
+__global__ void __launch_bounds__(64 * (PGW_MAX_AGENTS + 1)) k_coord_step_od_f32(
+    StepOdArgs A_, pgw_coord_step_info s, int64_t n, pgw_coord_buffers_f32 b, double pv_ob, StdDerived dv,
+    CoordPFArgs c, ODVLook o) {
+  typedef float F2 __attribute__((ext_vector_type(2)));
+  typedef int I2 __attribute__((ext_vector_type(2)));
+  const StepOdArgs& A = PGW_KERNARG0(StepOdArgs);               // (no private copy)
+  const pgw_coord_params& p = A.p;
+  const ODWaveArgs& z = A.z;
+  const int a = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const bool look = __builtin_amdgcn_readfirstlane(a) == c.n_agents;
+  const int64_t e = 2 * ((int64_t)blockIdx.x * 64 + lane);      // the lane's first env (n even)
+  const bool valid = e < n;
+  __shared__ double s_pow[PGW_MAX_AGENTS][128];
+  __shared__ double s_share[128];
+  __shared__ int s_served[128];
+  if (!look) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) b.od_count[(b.od_parity & 1) ^ 1] = 0;
+    float rw[2] = {0.0f, 0.0f};
+    StdAgentInEarly in[2];
+    float* xp = b.x + (int64_t)a * 5 * n + e;
+    float* socp = b.soc + (int64_t)a * n + e;
+    if (valid) {
+      const float* ap = b.action.ptr + a * b.act_stride_agent + e;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const F2 v = ld_act(reinterpret_cast<const F2*>(ap + j * b.action.s_dim));
+        in[0].av[j] = (double)v.x;
+        in[1].av[j] = (double)v.y;
+      }
+      {
+        const F2 v = *reinterpret_cast<const F2*>(socp);
+        in[0].soc = (double)v.x;
+        in[1].soc = (double)v.y;
+      }
+#pragma unroll
+      for (int z = 0; z < 5; ++z) {
+        const F2 v = *reinterpret_cast<const F2*>(xp + z * n);
+        in[0].xs[z] = (double)v.x;
+        in[1].xs[z] = (double)v.y;
+      }
+      std_agent_compute<2, 1>(p, dv, s, pv_ob, in, [&](int, const double (&v)[2]) {
+        const F2 w = {(float)v[0], (float)v[1]};
+        s_pow[a][2 * lane] = (double)w.x;            // the stored power, as the PF kernel reads it back
+        s_pow[a][2 * lane + 1] = (double)w.y;
+        *reinterpret_cast<F2*>(b.agent_power + (int64_t)a * n + e) = w;
+      });
+    }
+    __syncthreads();
+    if (valid) {
+      float* op = b.obs.ptr + a * b.obs_stride_agent + e;
+      std_agent_compute<2, 2>(p, dv, s, pv_ob, in, [&](int slot, const double (&v)[2]) {
+        const F2 w = {(float)v[0], (float)v[1]};
+        if (slot < kSlotSoc) *reinterpret_cast<F2*>(xp + slot * n) = w;
+        else if (slot == kSlotSoc) *reinterpret_cast<F2*>(socp) = w;
+        else if (slot < kSlotPower)
+          __builtin_nontemporal_store(w, reinterpret_cast<F2*>(op + (slot - kSlotObs) * b.obs.s_dim));
+        else {
+          rw[0] = w.x;
+          rw[1] = w.y;
+        }
+      });
+    }
+    __syncthreads();
+    if (!valid) return;
+    F2 r;
+    {
+      const bool f0 = c.coordinated && s_served[2 * lane], f1 = c.coordinated && s_served[2 * lane + 1];
+      r.x = f0 ? rw[0] + (float)(-s_share[2 * lane]) : rw[0];
+      r.y = f1 ? rw[1] + (float)(-s_share[2 * lane + 1]) : rw[1];
+    }
+    *reinterpret_cast<F2*>(b.reward + (int64_t)a * n + e) = r;
+    return;
+  }
+  // The lookup wave: no global memory access before the first barrier.
+  ODVLook ol = {o.resp_v, o.resp_x0, o.resp_inv_h, o.resp_nseg, 0};
+  int ctrl[PGW_MAX_AGENTS];
+#pragma unroll
+  for (int ag = 0; ag < PGW_MAX_AGENTS; ++ag) {
+    ctrl[ag] = c.agent_ctrl[ag];
+    asm volatile("" : "+s"(ctrl[ag]));
+  }
+  asm volatile("" : "+s"(ol.resp_x0), "+s"(ol.resp_inv_h), "+s"(ol.resp_nseg));
+  __syncthreads();
+  // both envs' bus loads (0 + p0 + p1 ... over the stored powers, widened),
+  // both cells and both node records before the first chain compare
+  double pc0 = 0.0, pc1 = 0.0;
+  ODVRec rec0, rec1;                                 // (read only where cell)
+  bool cell0 = false, cell1 = false;
+  if (valid) {
+#pragma unroll
+    for (int ag = 0; ag < PGW_MAX_AGENTS; ++ag) {
+      const int cs = ag < c.n_agents ? ctrl[ag] : -1;
+      const double pa0 = ag < c.n_agents ? s_pow[ag][2 * lane] * 1.0 : 0.0;
+      const double pa1 = ag < c.n_agents ? s_pow[ag][2 * lane + 1] * 1.0 : 0.0;
+      pc0 = (cs == 0) ? pc0 + pa0 : pc0;
+      pc1 = (cs == 0) ? pc1 + pa1 : pc1;
+    }
+    int r0 = 0, r1 = 0;
+    cell0 = !o.timing_only && od_resp_v_cell(ol, pc0, 0.0, r0);
+    cell1 = !o.timing_only && od_resp_v_cell(ol, pc1, 0.0, r1);
+    if (cell0) rec0 = od_resp_v_load(ol, r0);
+    if (cell1) rec1 = od_resp_v_load(ol, r1);
+  }
+  double2 vf0 = make_double2(0.0, 0.0), vf1 = make_double2(0.0, 0.0);
+  int it0 = 0, it1 = 0;
+  bool served0 = valid && cell0 && od_resp_v_chain(ol, pc0, rec0, vf0, it0);
+  bool served1 = valid && cell1 && od_resp_v_chain(ol, pc1, rec1, vf1, it1);
+  // the envs the table left, first halves then second halves: the wave's snap
+  // solve, one env at a time (the usual wave has none)
+  __shared__ ODWaveShared s_solve;
+  uint64_t left0 = __ballot(valid && !served0 && !o.timing_only);
+  uint64_t left1 = __ballot(valid && !served1 && !o.timing_only);
+  if (left0 | left1) {                               // (uniform)
+    if (lane == 0) atomicAdd(b.od_count + (b.od_parity & 1), __popcll(left0) + __popcll(left1));
+    od_wave_stage(z, s_solve);
+    do {
+      const bool second = left0 == 0;                // (uniform)
+      const int L = __builtin_ctzll(second ? left1 : left0);
+      if (second) left1 &= left1 - 1;
+      else left0 &= left0 - 1;
+      double v0r, v0i;
+      const int its = od_wave_solve(z, s_solve, wave_bcast(second ? pc1 : pc0, L), 0.0, v0r, v0i);
+      if (lane == L) {
+        if (second) {
+          vf1 = make_double2(v0r, v0i);
+          it1 = its;
+          served1 = true;
+        } else {
+          vf0 = make_double2(v0r, v0i);
+          it0 = its;
+          served0 = true;
+        }
+      }
+    } while (left0 | left1);
+  }
+  // |V675.3|, the violation and the share of both envs (fp64; rounded once at
+  // the stores); a pair both served stores 2-vectors
+  double share0 = 0.0, share1 = 0.0, vv0 = 0.0, vv1 = 0.0;
+  const double v00 = sqrt(fma(vf0.y, vf0.y, vf0.x * vf0.x));
+  const double v01 = sqrt(fma(vf1.y, vf1.y, vf1.x * vf1.x));
+  if (c.coordinated) {
+    vv0 = pymax(pymax(0.0, c.vv_lo - v00), v00 - c.vv_hi);
+    vv1 = pymax(pymax(0.0, c.vv_lo - v01), v01 - c.vv_hi);
+    if (served0) share0 = (vv0 * c.vv_penalty) / (double)c.n_agents;
+    if (served1) share1 = (vv1 * c.vv_penalty) / (double)c.n_agents;
+  }
+  if (served0 && served1) {
+    if (b.v_out) *reinterpret_cast<F2*>(b.v_out + e) = F2{(float)v00, (float)v01};
+    if (b.iters) *reinterpret_cast<I2*>(b.iters + e) = I2{it0, it1};
+    if (c.coordinated && b.vv) *reinterpret_cast<F2*>(b.vv + e) = F2{(float)vv0, (float)vv1};
+  } else {
+    if (served0) {
+      if (b.v_out) b.v_out[e] = (float)v00;
+      if (b.iters) b.iters[e] = it0;
+      if (c.coordinated && b.vv) b.vv[e] = (float)vv0;
+    }
+    if (served1) {
+      if (b.v_out) b.v_out[e + 1] = (float)v01;
+      if (b.iters) b.iters[e + 1] = it1;
+      if (c.coordinated && b.vv) b.vv[e + 1] = (float)vv1;
+    }
+  }
+  s_share[2 * lane] = share0;
+  s_share[2 * lane + 1] = share1;
+  s_served[2 * lane] = served0 ? 1 : 0;
+  s_served[2 * lane + 1] = served1 ? 1 : 0;
+  __syncthreads();
+}
+
 // The snap solve of the envs k_coord_step_od appended to its list (the table
 // did not serve them: P in a bracket or a guard zone, off the grid, an unfit
 // piece), grid-stride over the list with a small fixed grid: the list's count
@@ -3231,6 +3418,31 @@ static int32_t coord_step(const pgw_coord_params* p, const pgw_pf_params* pf, co
     if (b.od_count) {
       const hipError_t me = hipMemsetAsync(b.od_count + ((b.od_parity & 1) ^ 1), 0, sizeof(int32_t), st);
       PGW_REQUIRE(me == hipSuccess, "pgw_coord_step: od_count reset: %s", hipGetErrorString(me));
+    }
+  }
+  if constexpr (kF32) {
+    // the same one-launch step on fp32 buffers, env pairs (k_coord_step_od_f32:
+    // the inline form with plain stores only -- PGW_STEP_LIST / PGW_STEP_WT
+    // keep the two kernels); where the pair layout does not fit (pairs_ok, the
+    // lookup wave's 2-vector stores) the two kernels run and the next step's
+    // count is zeroed here
+    if (pft->od && b.od_list && b.od_count && !g_pf_trace_on.load() && !g_step_list && !g_step_wt && std_layout &&
+        pairs_ok(b, n) && ((reinterpret_cast<uintptr_t>(b.v_out) | reinterpret_cast<uintptr_t>(b.vv) |
+                            reinterpret_cast<uintptr_t>(b.iters)) & 7) == 0) {
+      const ODArgs o = make_od_args(*pft->od, pf->max_iter);
+      if (o.resp_v && o.resp_v_row == 0 && pf->n_out == 1 && p->vv_row == 0) {
+        const ODVLook lk = {o.resp_v, o.resp_x0, o.resp_inv_h, o.resp_nseg, g_step_nolookup ? 1 : 0};
+        const StepOdArgs sa = {*p, make_wave_args(a, o, *pf, *pft)};
+        // a block: one wave per agent and the lookup wave, over 64 env pairs
+        const dim3 grid((unsigned)((n / 2 + 63) / 64)), block(64 * (p->n_agents + 1));
+        launch_timed(PGW_T_COORD_AGENTS, k_coord_step_od_f32, grid, block, st, sa, *s, n, b, pv_ob,
+                     make_std_derived(*p), c, lk);
+        return check_launch("k_coord_step_od_f32");
+      }
+    }
+    if (b.od_count) {
+      const hipError_t me = hipMemsetAsync(b.od_count + ((b.od_parity & 1) ^ 1), 0, sizeof(int32_t), st);
+      PGW_REQUIRE(me == hipSuccess, "pgw_coord_step_f32: od_count reset: %s", hipGetErrorString(me));
     }
   }
   // fp32: env pairs per lane (float2 accesses).  The pair layout measured for

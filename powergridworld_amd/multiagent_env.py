@@ -81,20 +81,9 @@ class MultiAgentEnv(Env):
         self._times, self._end_step = [], 10 ** 12
         self._time_at(0)
 
-        self.agents = []
-        for a in agents:
-            _config = a["config"]
-            if "name" in a["config"]:
-                _config = {k: v for k, v in _config.items() if k != "name"}
-                logger.warning("ignoring 'name' in config dict in favor of constructor argument")
-            cls = resolve_env_class(a["cls"])
-            new_agent = cls(name=a["name"], num_envs=self.num_envs, device=self.device,
-                            **_config, **self.common_config)
-            self.agents.append(new_agent)
         # one out-of-bounds action counter for every component of every agent
         self.oob_count = torch.zeros(1, dtype=torch.int64, device=self.device)
-        for agent in self.agents:
-            agent._bind_oob(self.oob_count)
+        self._make_agents(agents, torch.float64)
         self.agent_name_bus_map = {a["name"]: a["bus"] for a in agents}
         self.agent_names = list(set([a.name for a in self.agents]))
         assert len(self.agent_names) == len(agents), "all agents need unique names"
@@ -120,7 +109,19 @@ class MultiAgentEnv(Env):
             if why is None:
                 self._setup_fused()
             else:
-                why_ma = self._ma_fusable() if self.dtype == torch.float64 else "fp32 storage"
+                if self.dtype != torch.float64:
+                    # not the C4 layout: the fused multi-agent step on fp32 agents
+                    # (pgw_ma_step_f32).  (The C4 fp32 step above keeps fp64
+                    # agents for their reset, _f32_sync.)
+                    try:
+                        self._make_agents(agents, self.dtype)
+                    except NotImplementedError as err:
+                        raise ValueError("dtype=%s: %s" % (self.dtype, err))
+                why_ma = self._ma_fusable()
+                if why_ma is not None and self.dtype != torch.float64:
+                    # no generic path on fp32 agents (its bus sums and power flow read fp64)
+                    raise ValueError("dtype=%s needs a fused path: %s; multi-agent step: %s"
+                                     % (self.dtype, why, why_ma))
                 if why_ma is None:
                     self._setup_ma()
                 elif fused is True:
@@ -134,6 +135,24 @@ class MultiAgentEnv(Env):
         self._hist = None
         if self.record_history:
             self._init_history(history_capacity)
+
+    def _make_agents(self, agents, dtype):
+        """The agents of the config list with storage `dtype` (fp64: the
+        classes' default, no dtype passed)."""
+        self.agents = []
+        for a in agents:
+            _config = a["config"]
+            if "name" in a["config"]:
+                _config = {k: v for k, v in _config.items() if k != "name"}
+                if dtype == torch.float64:       # (said once: the fp32 agents are a second pass)
+                    logger.warning("ignoring 'name' in config dict in favor of constructor argument")
+            if dtype != torch.float64:
+                _config = dict(_config, dtype=dtype)
+            cls = resolve_env_class(a["cls"])
+            new_agent = cls(name=a["name"], num_envs=self.num_envs, device=self.device,
+                            **_config, **self.common_config)
+            new_agent._bind_oob(self.oob_count)
+            self.agents.append(new_agent)
 
     # ================================================================ hooks
     @abstractmethod
@@ -367,7 +386,11 @@ class MultiAgentEnv(Env):
             return
         s_ = H["t"] % H["cap"]
         if self._fused is None:                # the fused kernels wrote the slot themselves
-            torch.stack(agent_power_p, out=H["p"][s_])
+            if agent_power_p[0].dtype == H["p"].dtype:
+                torch.stack(agent_power_p, out=H["p"][s_])
+            else:                              # fp32 agents (pgw_ma_step_f32): widened into the fp64 ring
+                for ai, p in enumerate(agent_power_p):
+                    H["p"][s_, ai].copy_(p)
         H["t"] += 1
         self.history["timestamp"].append(self.time)
         self.history["voltage"].append(H["vd"][s_])
@@ -519,7 +542,7 @@ class MultiAgentEnv(Env):
             full.calculate_power_flow(p_controllable_consumed={ctrl[k]: v for k, v in sums.items()},
                                       current_time=self.time)
         out = full.get_bus_voltages()
-        if self.dtype != torch.float64:
+        if self.dtype != torch.float64 and self._ma is None:    # (pgw_ma_step_f32: fp64 voltages)
             out = {k: v.to(self.dtype) for k, v in out.items()}
         return out
 
@@ -720,7 +743,8 @@ class MultiAgentEnv(Env):
         solver = self.pf_solver
         solver.set_controllable_loads(sorted(set(self.agent_name_bus_map.values())))
         ctrl = list(solver._ctrl_names)
-        args = _lib.MAStepArgs()
+        f32 = self.dtype != torch.float64
+        args = (_lib.MAStepArgsF32 if f32 else _lib.MAStepArgs)()
         ext = {"min_voltage": solver._vmin, "max_voltage": solver._vmax}
         plan, slot, n_pv = [], 0, 0
         for g, agent in enumerate(self.agents):
@@ -777,7 +801,7 @@ class MultiAgentEnv(Env):
         self._ma = {"args": args, "plan": plan, "bus_p": bus_p, "ctrl": ctrl, "calls": calls,
                     "iters": torch.zeros(n, dtype=torch.int32, device=dev),
                     "lazy_v": _FusedVoltages(self, {}, 0), "bufv": self._ma_bufv(plan),
-                    "gen": ComponentEnv._bufv_gen, "fn": _lib.lib().pgw_ma_step,
+                    "gen": ComponentEnv._bufv_gen, "fn": _lib.lib().pgw_ma_step_f32 if f32 else _lib.lib().pgw_ma_step,
                     "general": _lib.lib().pgw_pf_solve_general if solver.general else None}
 
     @staticmethod
@@ -854,17 +878,18 @@ class MultiAgentEnv(Env):
         return obs, rew, done, meta
 
     def _one_launch_ok(self):
-        """The fused C4 step can run as one launch (k_coord_step_od): fp64, the
+        """The fused C4 step can run as one launch (k_coord_step_od, or on fp32
+        buffers k_coord_step_od_f32): the
         OpenDSS rule on the fast kernel with the hour's response table and node
         records, the coordinated bus the only output row, the standard agent."""
         s = self.pf_solver
-        return (self.dtype == torch.float64 and getattr(s, "convergence", None) == "opendss" and
+        return (getattr(s, "convergence", None) == "opendss" and
                 bool(getattr(s, "od_table", False)) and bool(getattr(s, "od_node_records", False)) and
                 not getattr(s, "general", True) and len(s.output_names) == 1 and
                 self.fused_reward_transform == "coordinated" and self._f32_fusable() is None)
 
     def set_pf_list(self, enabled=True):
-        """Fused C4 step under the OpenDSS rule with node records (fp64): True
+        """Fused C4 step under the OpenDSS rule with node records: True
         (the default where _one_launch_ok) runs it as ONE launch,
         k_coord_step_od -- the agents, the table lookup and, for the rare envs
         the table leaves, the snap solve by the lookup wave (od_wave_solve);
@@ -873,9 +898,14 @@ class MultiAgentEnv(Env):
         the second launch's ~4.6 us boundary.
         od_count[od_parity] counts the envs the step left to the solve.  (The
         library's PGW_STEP_LIST=1 runs the older list form instead: those envs
-        listed and solved by k_coord_pf_od_list in a second launch.)"""
+        listed and solved by k_coord_pf_od_list in a second launch.)
+        fp32 storage: the one launch is k_coord_step_od_f32 (an env pair per
+        lane), bit-identical to the fp32 two-kernel step; with an odd num_envs
+        or packed actions that are not env-minor with even strides -- and with
+        PGW_STEP_LIST=1 or PGW_STEP_WT=1 -- the library runs the two kernels
+        whatever is set here, and od_count stays 0."""
         F = self._fused
-        if F is None or self.dtype != torch.float64:
+        if F is None:
             return
         b = F["bufs"]
         if enabled:

@@ -32,17 +32,24 @@ class ThisPVEnv(PVEnv):
 
     def _band_buffer(self):
         if self.__dict__.get("_band_rew") is None:
-            self._band_rew = torch.empty(self.num_envs, dtype=torch.float64, device=self.device)
+            self._band_rew = torch.empty(self.num_envs, dtype=self.dtype, device=self.device)
         return self._band_rew
 
     def step_reward(self, **kwargs):
         v = as_env_tensor(kwargs["min_voltage"], self.num_envs, self.device, "min_voltage")
-        self._band_buffer()
+        rew = self._band_buffer()
+        out = rew
+        if self.dtype != torch.float64:          # the kernel writes fp64: rounded once, at the copy
+            if self.__dict__.get("_band_rew64") is None:
+                self._band_rew64 = torch.empty(self.num_envs, dtype=torch.float64, device=self.device)
+            out = self._band_rew64
         lo, hi, scale = self.fused_band_reward
         # one kernel: -(1000 (min(0, v - 0.95) + min(0, 1.05 - v)))^2
         _lib.check(_lib.lib().pgw_voltage_band_penalty(self.num_envs, v.data_ptr(), lo, hi, scale,
-                                                        self._band_rew.data_ptr(), self._stream()))
-        return self._band_rew, {}
+                                                        out.data_ptr(), self._stream()))
+        if out is not rew:
+            rew.copy_(out)
+        return rew, {}
 
 
 def make_env_config(system_load_rescale_factor=0.65, rescale_spaces=True, pf_convergence="opendss"):

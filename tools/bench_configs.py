@@ -9,7 +9,8 @@ inside the timed region.  One JSON line per config.
 Usage: python tools/bench_configs.py [--configs C2,C3,HET,HETG,HS,...] [--steps K] [--warmup W]
 (HET: OpenDSS's snap-solve rule, the default, with its response table; HETS:
 every env solved; HETX: the exact fixed point; HETG: the heterogeneous scenario
-on the generic path, fused=False; C3F / C3G8F:
+on the generic path, fused=False; HETF: HET with fp32 storage
+(pgw_ma_step_f32); C3F / C3G8F:
 C3 with fp32 storage (pgw_mc_agent_step_f32); C3L: C3 at
 65 536 envs; C2Gk / C3Gk: the step replayed from captured hipGraphs of k steps,
 C3 through the device clocks; C3Pk / HSPk: captured once per episode position,
@@ -145,10 +146,10 @@ def bench_c3(dev, steps, warmup, n=16384, pool=16, graph=0, clocked=True, dtype=
 
 
 def bench_het(dev, steps, warmup, n=65536, pool=16, fused="auto", conv="opendss", table=True, vrec=True, qrec=True,
-              rrows=True):
+              rrows=True, dtype=torch.float64):
     from powergridworld_amd.scenarios.heterogeneous import make_env_config
     from powergridworld_amd.multiagent_env import MultiAgentEnv
-    env = MultiAgentEnv(**make_env_config(pf_convergence=conv), num_envs=n, device=dev, fused=fused)
+    env = MultiAgentEnv(**make_env_config(pf_convergence=conv), num_envs=n, device=dev, fused=fused, dtype=dtype)
     env.pf_solver.od_table = table
     if hasattr(env.pf_solver, "od_node_records"):
         env.pf_solver.od_node_records = vrec
@@ -159,10 +160,10 @@ def bench_het(dev, steps, warmup, n=65536, pool=16, fused="auto", conv="opendss"
     gen = torch.Generator(dev).manual_seed(0)
     acts = []
     for _ in range(pool):
-        acts.append({a.name: ({c.name: torch.empty((n, c.action_space.shape[0]), dtype=torch.float64,
+        acts.append({a.name: ({c.name: torch.empty((n, c.action_space.shape[0]), dtype=dtype,
                                                     device=dev).uniform_(-1, 1, generator=gen)
                                for c in a.envs} if hasattr(a, "envs") else
-                              torch.empty((n, a.action_space.shape[0]), dtype=torch.float64,
+                              torch.empty((n, a.action_space.shape[0]), dtype=dtype,
                                           device=dev).uniform_(-1, 1, generator=gen))
                      for a in env.agents})
     k = [0]
@@ -174,9 +175,11 @@ def bench_het(dev, steps, warmup, n=65536, pool=16, fused="auto", conv="opendss"
 
     dt = timed_loop(env, step, env.reset, steps, warmup)
     return dict(config=("HET" if fused else "HETG") + ("X" if conv == "exact" else "") + ("" if table else "S")
-                + ("" if vrec else "V") + ("" if qrec else "Q") + ("" if rrows else "R"),
+                + ("" if vrec else "V") + ("" if qrec else "Q") + ("" if rrows else "R")
+                + ("F" if dtype == torch.float32 else ""),
                 workload="3-agent heterogeneous (MC building, grid-aware PV farm, EV 25x40) + IEEE-13 PF, "
-                         + ("fused multi-agent step (pgw_ma_step)" if env._ma is not None else "generic path"),
+                         + ("fused multi-agent step (pgw_ma_step%s)" % ("_f32" if dtype == torch.float32 else "")
+                            if env._ma is not None else "generic path"),
                 pf_convergence=conv, pf_response_table=bool(table and conv == "opendss"),
                 batch=n, agents=3, steps=steps, seconds=dt)
 
@@ -229,6 +232,7 @@ def main():
            "HETV": lambda *a: bench_het(*a, vrec=False),
            "HETQ": lambda *a: bench_het(*a, qrec=False),
            "HETR": lambda *a: bench_het(*a, rrows=False),
+           "HETF": lambda *a: bench_het(*a, dtype=torch.float32),
            "C2G1": lambda *a: bench_c2(*a, graph=1), "C2G8": lambda *a: bench_c2(*a, graph=8),
            "C3G1": lambda *a: bench_c3(*a, graph=1), "C3G8": lambda *a: bench_c3(*a, graph=8),
            "C3P1": lambda *a: bench_c3(*a, graph=1, clocked=False),
