@@ -62,7 +62,9 @@ typedef struct pgw_mat {
  * actions and outputs as fp32 (half the HBM bytes) but compute in fp64
  * registers: each value is widened on load and rounded once at its store, so
  * the only deviation from the fp64 path is the storage rounding (~6e-8 rel per
- * step; the north-star bound for fp32 is 1e-3 rel). */
+ * step; the north-star bound for fp32 is 1e-3 rel).  Voltages an f32 entry
+ * takes from the power flow (min_voltage of pgw_pv_obs_f32 and of the
+ * Home-Steward house's pgw_hs_*_f32) stay double. */
 typedef struct pgw_matf {
   float* ptr;
   int64_t s_env;
@@ -1294,6 +1296,47 @@ int32_t pgw_hs_reset(const pgw_hs_params* p, const pgw_hs_step_info* s, int64_t 
  * and the house reward. */
 int32_t pgw_hs_step(const pgw_hs_params* p, const pgw_hs_step_info* s, int64_t n,
                     pgw_hs_buffers b, void* stream);
+
+/* fp32-storage house: pgw_hs_buffers with 4-byte elements -- the same field
+ * names, order, offsets and size (every field is a pointer or a pgw_mat[f]),
+ * so a binding derives it from pgw_hs_buffers; it is not in pgw_struct_sizes.
+ * Rounding contract: every per-env value (action, SoC, stored / EV / device
+ * cost, ev_req, es_power_last, pv_power_last -- NaN stays NaN) is widened to
+ * fp64 on load, the whole chain runs in the fp64 arithmetic of pgw_hs_step, op
+ * for op, and every store (obs, the state above, reward, real_power, meta_out,
+ * each step_meta field) rounds once to fp32.  So one step from the same
+ * (fp32-representable) state gives exactly RN32 of the fp64 entry's outputs.
+ * ev_charging is the same bit mask.  min_voltage stays fp64: it is the fp64
+ * power flow's output, as for pgw_pv_obs_f32. */
+typedef struct pgw_hs_buffers_f32 {
+  pgw_matf action;
+  pgw_matf obs;
+  float* soc;
+  float* soc_cost;
+  float* ev_req;
+  uint64_t* ev_charging;
+  float* ev_cost;
+  float* dev_cost;
+  float* es_power_last;
+  float* reward;
+  float* real_power;
+  float* meta_out;
+  float* step_meta;
+  float* pv_power_last;       /* NaN = the reference's initial None        */
+  const double* min_voltage;  /* fp64, see above                           */
+} pgw_hs_buffers_f32;
+
+/* reset (base_hs.py:66-91, energy_storage_env_hs.py:76-98): as pgw_hs_reset;
+ * init_soc is n floats (as pgw_battery_reset_f32), SoC := RN32(clip(init_soc)),
+ * ev_req restored from p->ev_req0 (doubles) rounded once
+ * (ev_charging_env_hs.py:127-145). */
+int32_t pgw_hs_reset_f32(const pgw_hs_params* p, const pgw_hs_step_info* s, int64_t n,
+                         const float* init_soc, pgw_hs_buffers_f32 b, void* stream);
+/* step (base_hs.py:114-180 over pv_profile_env_hs.py:122-160,
+ * energy_storage_env_hs.py:189-270, ev_charging_env_hs.py:182-326,
+ * devices_env_hs.py:147-205): as pgw_hs_step, fp32 storage. */
+int32_t pgw_hs_step_f32(const pgw_hs_params* p, const pgw_hs_step_info* s, int64_t n,
+                        pgw_hs_buffers_f32 b, void* stream);
 
 #ifdef __cplusplus
 }

@@ -303,6 +303,13 @@ class HSBuffers(C.Structure):
                 ("pv_power_last", vp), ("min_voltage", vp)]
 
 
+class HSBuffersF32(C.Structure):
+    """pgw_hs_buffers_f32: pgw_hs_buffers with fp32 per-env buffers (the same
+    field names and layout; min_voltage stays fp64, ev_charging a bit mask).
+    Not in STRUCTS: libpgw static_asserts its layout against pgw_hs_buffers."""
+    _fields_ = [(nm, Matf) if tp is Mat else (nm, tp) for nm, tp in HSBuffers._fields_]
+
+
 class ODCertifyModel(C.Structure):
     """pgw_od_certify_model: the snap solve's model for pgw_pf_od_certify (od_certify.SnapModel)."""
     _fields_ = [(k, vp) for k in ("u1b", "u1P", "J0", "jP", "s0", "fr", "y0", "u0", "W", "Wa", "G", "Ga", "V0")] + \
@@ -380,6 +387,8 @@ _SIGS = {
     "pgw_graph_launch": (i32, [vp, vp]),
     "pgw_graph_destroy": (i32, [vp]),
     "pgw_hs_step": (i32, [P(HSParams), P(HSStepInfo), i64, HSBuffers, vp]),
+    "pgw_hs_reset_f32": (i32, [P(HSParams), P(HSStepInfo), i64, vp, HSBuffersF32, vp]),
+    "pgw_hs_step_f32": (i32, [P(HSParams), P(HSStepInfo), i64, HSBuffersF32, vp]),
     "pgw_ma_step": (i32, [P(MAStepArgs), P(PFParams), P(PFTables), i64, vp, vp, vp]),
     "pgw_ma_step_f32": (i32, [P(MAStepArgsF32), P(PFParams), P(PFTables), i64, vp, vp, vp]),
 }

@@ -7,6 +7,9 @@ chain in one kernel (pgw_hs_step): each class here holds its component's
 parameters, spaces and obs labels exactly as the reference builds them, and
 the house hands it views of its state.  Stepping one on its own is not
 supported -- the reference's components need the house's meta_state kwargs.
+
+dtype=torch.float32 (given by the house to every component): the component's
+state and observation views are fp32, stepped by pgw_hs_step_f32.
 """
 import json
 import math
@@ -31,6 +34,7 @@ def load_hs_data():
 
 class _HSComponent(ComponentEnv):
     hs_kind = None
+    supported_dtypes = (torch.float64, torch.float32)
 
     def reset(self, **kwargs):
         raise NotImplementedError("%s resets inside HSMultiComponentEnv" % type(self).__name__)
@@ -58,8 +62,8 @@ class HSPVEnv(_HSComponent):
     def __init__(self, name: str = None, profile_csv: str = None, profile_path: str = None,
                  profile_data: list = [], scaling_factor: float = 1., rescale_spaces: bool = True,
                  grid_aware: bool = False, max_episode_steps: int = None, minutes_per_step: int = 5,
-                 num_envs: int = 1, device=None, **kwargs):
-        super().__init__(name=name, num_envs=num_envs, device=device)
+                 num_envs: int = 1, device=None, dtype=None, **kwargs):
+        super().__init__(name=name, num_envs=num_envs, device=device, dtype=dtype)
         self.grid_aware = bool(grid_aware)
         self.scaling_factor = scaling_factor
         self.rescale_spaces = rescale_spaces
@@ -97,8 +101,8 @@ class HSEnergyStorageEnv(_HSComponent):
                  discharge_efficiency: float = 0.9, max_power: float = 15.0, max_episode_steps: int = 288,
                  control_timedelta: pd.Timedelta = pd.Timedelta(300, "s"), rescale_spaces: bool = True,
                  initial_storage_cost: float = 0.0, max_storage_cost: float = 0.55, num_envs: int = 1,
-                 device=None, **kwargs):
-        super().__init__(name=name, num_envs=num_envs, device=device)
+                 device=None, dtype=None, **kwargs):
+        super().__init__(name=name, num_envs=num_envs, device=device, dtype=dtype)
         self.initial_storage_cost = initial_storage_cost
         self.storage_range = tuple(storage_range)
         self.initial_storage_mean = initial_storage_mean
@@ -119,8 +123,8 @@ class HSEnergyStorageEnv(_HSComponent):
         self._action_space = spaces.Box(shape=(1,), low=-1.0, high=1.0, dtype=np.float64)
         self.action_space = maybe_rescale_box_space(self._action_space, rescale_spaces)
         n = self.num_envs
-        self.soc = torch.zeros(n, dtype=torch.float64, device=self.device)
-        self.cost = torch.full((n,), float(initial_storage_cost), dtype=torch.float64, device=self.device)
+        self.soc = torch.zeros(n, dtype=self.dtype, device=self.device)
+        self.cost = torch.full((n,), float(initial_storage_cost), dtype=self.dtype, device=self.device)
         self._gen = torch.Generator(device=self.device)
         self.seed(None)
 
@@ -137,7 +141,8 @@ class HSEnergyStorageEnv(_HSComponent):
         truncnorm(-1, 1) * std + mean, drawn on the device by inverse-CDF sampling
         (z = sqrt(2) erfinv(2 u' - 1), u' ~ U[Phi(-1), Phi(1)]), as
         EnergyStorageEnv does: scipy's host sampler cost ~4 ms per reset at
-        65 536 envs (14 us per step of a 286-step episode)."""
+        65 536 envs (14 us per step of a 286-step episode).  Always fp64: the
+        fp32 house rounds it once, into its init_soc buffer."""
         if init_storage is None:
             lo = 0.5 * (1.0 + math.erf(-1.0 / math.sqrt(2.0)))
             hi = 0.5 * (1.0 + math.erf(1.0 / math.sqrt(2.0)))
@@ -168,8 +173,8 @@ class HSEVChargingEnv(_HSComponent):
                  peak_threshold: float = 10., reward_scale: float = 1e5, name: str = None,
                  randomize: bool = False, vehicle_csv: str = None, vehicle_multiplier: int = 1,
                  rescale_spaces: bool = True, max_charge_cost: float = 0.55, profile_data: dict = {},
-                 num_envs: int = 1, device=None, **kwargs):
-        super().__init__(name=name, num_envs=num_envs, device=device)
+                 num_envs: int = 1, device=None, dtype=None, **kwargs):
+        super().__init__(name=name, num_envs=num_envs, device=device, dtype=dtype)
         self.num_vehicles = num_vehicles
         self.max_charge_rate_kw = max_charge_rate_kw
         self.minutes_per_step = minutes_per_step
@@ -225,8 +230,8 @@ class HSDevicesEnv(_HSComponent):
     def __init__(self, name: str = None, profile_csv: str = None, profile_path: str = None,
                  profile_data: dict = {}, scaling_factor: float = 1., rescale_spaces: bool = True,
                  max_episode_steps: int = None, minutes_per_step: int = 5, num_envs: int = 1, device=None,
-                 **kwargs):
-        super().__init__(name=name, num_envs=num_envs, device=device)
+                 dtype=None, **kwargs):
+        super().__init__(name=name, num_envs=num_envs, device=device, dtype=dtype)
         self.scaling_factor = scaling_factor
         self.rescale_spaces = rescale_spaces
         self.minutes_per_step = minutes_per_step

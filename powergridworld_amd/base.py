@@ -322,6 +322,11 @@ class MultiComponentEnv(ComponentEnv):
         self._reward = torch.zeros(self.num_envs, dtype=self.dtype, device=self.device)
         if len(self.envs) > _lib.MAX_COMP:
             raise ValueError("at most %d components per agent" % _lib.MAX_COMP)
+        self._require_storage_variant()
+
+    def _require_storage_variant(self):
+        """Refuse a storage dtype this agent has no kernel for (fp32: the fused
+        step only; the Home-Steward house, with a kernel of its own, overrides)."""
         if self.dtype != torch.float64 and not self._mc_fusable():
             raise NotImplementedError("MultiComponentEnv dtype=%s needs every component to be a fused kind "
                                       "(pgw_mc_agent_step_f32)" % self.dtype)

@@ -9,12 +9,21 @@ it drew feeds its reward.  The reference passes that state down the chain in a
 whatever the number of envs.
 
 Differences from the reference, all of them batching:
-  * obs / reward / real_power are [N] / [N, dim] fp64 device tensors (views of
-    the house's buffers: copy them to keep them across steps);
+  * obs / reward / real_power are [N] / [N, dim] device tensors of the house's
+    dtype (views of the house's buffers: copy them to keep them across steps);
   * the returned meta is the batched meta_state: timestamp and grid_cost
-    (shared), pv_power / es_power / grid_power ([N]); the per-device
-    `step_meta` logging records are not produced;
+    (shared), pv_power / es_power / grid_power ([N]); meta["step_meta"] holds
+    the per-device logging records with [N] tensors for the numeric fields
+    (step_meta=False leaves them out);
   * reset(init_storage=...) accepts a per-env [N] SoC.
+
+dtype=torch.float32: the fp32-storage house (pgw_hs_reset_f32 / pgw_hs_step_f32).
+Every per-env buffer -- actions, observations, SoC and costs, EV requirements,
+the carried es / pv power, reward, real power, meta and the step_meta records --
+is fp32; the kernel widens each value on load, runs the same fp64 chain and
+rounds once at each store, so a step from the same state gives exactly the
+fp32 rounding of the fp64 house's outputs.  min_voltage stays fp64 (the power
+flow's output), ev_charging a bit mask.
 """
 from typing import List
 
@@ -52,10 +61,10 @@ class HSMultiComponentEnv(MultiComponentEnv):
     def __init__(self, name: str = None, components: List[dict] = None, start_time: str = "",
                  end_time: str = "", control_timedelta=pd.Timedelta(300, "s"), max_grid_power: float = 48,
                  max_episode_steps: int = None, rescale_spaces: bool = True, num_envs: int = 1,
-                 device=None, step_meta: bool = True, **kwargs):
+                 device=None, step_meta: bool = True, dtype=None, **kwargs):
         self.max_grid_power = max_grid_power
         self._want_step_meta = bool(step_meta)
-        super().__init__(name=name, components=components, num_envs=num_envs, device=device)
+        super().__init__(name=name, components=components, num_envs=num_envs, device=device, dtype=dtype)
         from powergridworld_amd.agents.hs import _HSComponent
         self.rescale_spaces = rescale_spaces
         self._grid_cost_data = [float(x) for x in kwargs["grid_cost"]]
@@ -81,6 +90,11 @@ class HSMultiComponentEnv(MultiComponentEnv):
         self.meta_state = {"timestamp": None, "grid_cost": None, "es_cost": 0.0, "grid_power": None,
                            "pv_power": None, "es_power": None, "pv_cost": 0.0}
         self._setup()
+
+    def _require_storage_variant(self):
+        """The house steps through its own kernel (pgw_hs_step[_f32]), not the
+        fused agent step: both storage dtypes exist whatever the chain (the
+        constructor has checked that the components share the house's dtype)."""
 
     # ------------------------------------------------------------ buffers, params
     def _setup(self):
@@ -134,28 +148,30 @@ class HSMultiComponentEnv(MultiComponentEnv):
         self.params = p
         self._bind_oob(self.oob_count)
 
-        f64 = dict(dtype=torch.float64, device=dev)
-        self._obs_buf = torch.zeros((self._obs_dim, n), **f64)
-        self._act_buf = torch.zeros((len(self.envs), n), **f64)
+        f32 = self.dtype == torch.float32
+        Mat = _lib.Matf if f32 else _lib.Mat
+        buf = dict(dtype=self.dtype, device=dev)        # every per-env buffer: the house's dtype
+        self._obs_buf = torch.zeros((self._obs_dim, n), **buf)
+        self._act_buf = torch.zeros((len(self.envs), n), **buf)
         for c, e in enumerate(self.envs):
             e._adopt(self._obs_buf[p.obs_off[c]:p.obs_off[c] + dims[c]].t())
-        st_soc = st.soc if st is not None else torch.zeros(n, **f64)
-        st_cost = st.cost if st is not None else torch.zeros(n, **f64)
-        self._ev_req = torch.zeros((max(p.n_veh, 1), n), **f64)
+        st_soc = st.soc if st is not None else torch.zeros(n, **buf)
+        st_cost = st.cost if st is not None else torch.zeros(n, **buf)
+        self._ev_req = torch.zeros((max(p.n_veh, 1), n), **buf)
         self._ev_chg = torch.zeros(n, dtype=torch.int64, device=dev)
-        self._ev_cost = torch.zeros(n, **f64)
-        self._dev_cost = torch.zeros(n, **f64)
-        self._es_last = torch.zeros(n, **f64)       # meta_state es_power = 0.0 (base_hs.py:59)
+        self._ev_cost = torch.zeros(n, **buf)
+        self._dev_cost = torch.zeros(n, **buf)
+        self._es_last = torch.zeros(n, **buf)       # meta_state es_power = 0.0 (base_hs.py:59)
         # meta_state pv_power (base_hs.py:58: None until the PV's first step; NaN here):
         # carried from step to step, so components ahead of the PV see the last one
-        self._pv_last = torch.full((n,), float("nan"), **f64)
+        self._pv_last = torch.full((n,), float("nan"), **buf)
         self._mv_state = None          # meta_state min_voltage (set by the first step)
-        self._reward = torch.zeros(n, **f64)
-        self._meta = torch.zeros((3, n), **f64)
-        self._init_soc = torch.zeros(n, **f64)
-        b = _lib.HSBuffers()
-        b.action = _lib.Mat(self._act_buf.data_ptr(), 1, n)
-        b.obs = _lib.Mat(self._obs_buf.data_ptr(), 1, n)
+        self._reward = torch.zeros(n, **buf)
+        self._meta = torch.zeros((3, n), **buf)
+        self._init_soc = torch.zeros(n, **buf)
+        b = (_lib.HSBuffersF32 if f32 else _lib.HSBuffers)()
+        b.action = Mat(self._act_buf.data_ptr(), 1, n)
+        b.obs = Mat(self._obs_buf.data_ptr(), 1, n)
         b.soc, b.soc_cost = st_soc.data_ptr(), st_cost.data_ptr()
         b.ev_req, b.ev_charging = self._ev_req.data_ptr(), self._ev_chg.data_ptr()
         b.ev_cost, b.dev_cost = self._ev_cost.data_ptr(), self._dev_cost.data_ptr()
@@ -165,7 +181,7 @@ class HSMultiComponentEnv(MultiComponentEnv):
         b.meta_out = self._meta.data_ptr()
         self._step_meta = None
         if self._want_step_meta:
-            self._rec_buf = torch.zeros((len(self.envs), HS_META_FIELDS, n), **f64)
+            self._rec_buf = torch.zeros((len(self.envs), HS_META_FIELDS, n), **buf)
             b.step_meta = self._rec_buf.data_ptr()
             self._step_meta = []
             for c, (k, e) in enumerate(zip(self._kinds, self.envs)):
@@ -176,6 +192,8 @@ class HSMultiComponentEnv(MultiComponentEnv):
         self._bufs = b
         self._keep = (st_soc, st_cost)
         self._act_key = None
+        self._mat_cls = Mat
+        self._fn_reset, self._fn_step = self._kernel("pgw_hs_reset"), self._kernel("pgw_hs_step")
         self._info_cache = {}
         if dv is not None:
             self._dev_power = self._dev_rows(dv)
@@ -241,8 +259,8 @@ class HSMultiComponentEnv(MultiComponentEnv):
             ev.time = t0 = ev.simulation_times[0]
         s = self._info(t0, t0)
         self._bind_min_voltage(kwargs)
-        _lib.check(_lib.lib().pgw_hs_reset(self.params, s, self.num_envs, _lib.dptr(self._init_soc),
-                                           self._bufs, self._stream()))
+        _lib.check(self._fn_reset(self.params, s, self.num_envs, _lib.dptr(self._init_soc), self._bufs,
+                                  self._stream()))
         if ev is not None:
             ev.time = ev.simulation_times[ev.time_index]
             ev.time_index += 1
@@ -273,18 +291,22 @@ class HSMultiComponentEnv(MultiComponentEnv):
         return {e.name: e._obs for e in self.envs}, {}
 
     def _pack(self, action):
-        """A packed [N, n_comp] tensor is read in place (any strides); a
-        {component: [N, 1]} dict is gathered into the house's action buffer."""
+        """A packed [N, n_comp] tensor of the house's dtype is read in place
+        (any strides; another dtype or device is converted); a {component:
+        [N, 1]} dict is gathered into the house's action buffer."""
         if isinstance(action, torch.Tensor):
             if tuple(action.shape) != (self.num_envs, len(self.envs)):
                 raise ValueError("packed HS action must be [N, %d]" % len(self.envs))
-            if action.dtype != torch.float64 or action.device != self.device:
-                action = action.to(device=self.device, dtype=torch.float64)
+            if action.dtype != self.dtype or action.device != self.device:
+                action = action.to(device=self.device, dtype=self.dtype)
             key = (action.data_ptr(), action.stride(0), action.stride(1))
-            self._act_hold = action
+            # alive until the next step; not state: a restore that copied a saved
+            # tensor into it would overwrite the caller's own action tensor
+            # (checkpoint.py skips *keepalive*)
+            self._act_keepalive = action
         else:
             for c, e in enumerate(self.envs):
-                self._act_buf[c].copy_(as_action(action[e.name], self.num_envs, 1, self.device)[:, 0])
+                self._act_buf[c].copy_(as_action(action[e.name], self.num_envs, 1, self.device, self.dtype)[:, 0])
             key = (self._act_buf.data_ptr(), 1, self.num_envs)
         if key != self._act_key:                  # (Mats cached per buffer: callers cycle a few)
             mats = self.__dict__.setdefault("_act_mats", {})
@@ -292,7 +314,7 @@ class HSMultiComponentEnv(MultiComponentEnv):
             if m is None:
                 if len(mats) >= 64:
                     mats.clear()
-                m = mats[key] = _lib.Mat(*key)
+                m = mats[key] = self._mat_cls(*key)
             self._bufs.action = m
             self._act_key = key
 
@@ -302,7 +324,7 @@ class HSMultiComponentEnv(MultiComponentEnv):
         ev_time, ev_next = self._pre_step()
         s = self._info(ev_time, ev_next)
         self._bind_min_voltage(kwargs, stepping=True)
-        _lib.check(_lib.lib().pgw_hs_step(self.params, s, self.num_envs, self._bufs, self._stream()))
+        _lib.check(self._fn_step(self.params, s, self.num_envs, self._bufs, self._stream()))
         return self._post_step(ev_next)
 
     def _pre_step(self):
@@ -339,7 +361,8 @@ class HSMultiComponentEnv(MultiComponentEnv):
 
     def capture_step(self, action, steps=1, **kwargs):
         """A StepGraph (graph.py) of `steps` house steps reading `action` (a
-        packed [N, n_comp] fp64 device tensor, or a list of `steps` of them),
+        packed [N, n_comp] device tensor of the house's dtype, or a list of
+        `steps` of them),
         captured once per episode position on first use."""
         from powergridworld_amd.graph import StepGraph
         return StepGraph(self, action, steps, kwargs)

@@ -5,9 +5,28 @@
 // in registers and the components run in chain order.  Every expression
 // follows the reference's operation order (built with -ffp-contract=off), and
 // Python's min/max/round semantics are spelled out (pgw_common.h pymin/pymax).
+//
+// fp32 storage (pgw_hs_reset_f32 / pgw_hs_step_f32): k_hs is a template over
+// its buffer struct.  Every per-env value is widened to fp64 on load and
+// rounded once, (T)v, at its store; the chain's arithmetic below is the same
+// fp64 code for both instances.
 #include <cmath>
+#include <cstddef>
+#include <type_traits>
 
 #include "pgw_common.h"
+
+// pgw_hs_buffers_f32 is pgw_hs_buffers with 4-byte elements: same fields, same
+// layout (the host binding derives one struct from the other)
+#define PGW_HS_SAME(f)                                                             \
+  static_assert(offsetof(pgw_hs_buffers_f32, f) == offsetof(pgw_hs_buffers, f) && \
+                sizeof(pgw_hs_buffers_f32::f) == sizeof(pgw_hs_buffers::f), "pgw_hs_buffers_f32." #f)
+static_assert(sizeof(pgw_hs_buffers_f32) == sizeof(pgw_hs_buffers), "pgw_hs_buffers_f32 size");
+PGW_HS_SAME(action); PGW_HS_SAME(obs); PGW_HS_SAME(soc); PGW_HS_SAME(soc_cost); PGW_HS_SAME(ev_req);
+PGW_HS_SAME(ev_charging); PGW_HS_SAME(ev_cost); PGW_HS_SAME(dev_cost); PGW_HS_SAME(es_power_last);
+PGW_HS_SAME(reward); PGW_HS_SAME(real_power); PGW_HS_SAME(meta_out); PGW_HS_SAME(step_meta);
+PGW_HS_SAME(pv_power_last); PGW_HS_SAME(min_voltage);
+#undef PGW_HS_SAME
 
 namespace pgw {
 
@@ -24,11 +43,13 @@ struct HSState {
 };
 
 // One chain slot's step_meta record (PGW_HS_META_FIELDS in pgw.h); off = NULL.
+// T: the storage type (double, or float: rounded once here).
+template <class T>
 struct HSRec {
-  double* p;
+  T* p;
   int64_t n, e;
   __device__ __forceinline__ void put(int f, double v) const {
-    if (p) p[(int64_t)f * n + e] = v;
+    if (p) p[(int64_t)f * n + e] = (T)v;
   }
   // cost, reward, action, solar / es / grid power consumed
   __device__ __forceinline__ void common(double cost, double rew, double a, double sc, double bc,
@@ -40,9 +61,10 @@ struct HSRec {
 // HSPVEnv (pv_profile_env_hs.py:96-160): obs before the advance; the curtailed
 // power a * data[index] becomes meta_state pv_power (rew_meta, :146).
 // Grid-aware (:81-85, 110-111): min_voltage appended to the obs, box (0.9, 1.1).
+template <class Rec>
 __device__ __forceinline__ void hs_pv(const pgw_hs_params& p, const pgw_hs_step_info& s, int rescale,
                                       bool reset, double a, double vmin, HSMeta& M, double& rp, double* ob,
-                                      const HSRec& R) {
+                                      const Rec& R) {
   ob[0] = rescale ? to_scaled(-s.pv_avail, p.pv_obs_low, 0.0) : -s.pv_avail;
   ob[1] = rescale ? to_scaled(vmin, 0.9, 1.1) : vmin;
   if (reset) {
@@ -64,8 +86,9 @@ __device__ __forceinline__ void hs_pv(const pgw_hs_params& p, const pgw_hs_step_
 __device__ __forceinline__ double hs_storage_reward(const pgw_hs_params& p, const HSMeta& M, const HSState& S,
                                                     double rp, double* cost_out = nullptr);
 
+template <class Rec>
 __device__ __forceinline__ void hs_storage(const pgw_hs_params& p, const pgw_hs_step_info& s, int rescale,
-                                           double a, HSMeta& M, HSState& S, double& rp, const HSRec& R) {
+                                           double a, HSMeta& M, HSState& S, double& rp, const Rec& R) {
   const double pv_cap = M.pv, grid_cap = M.grid;
   double sc = 0.0, gc = 0.0;
   if (rescale) {
@@ -137,9 +160,11 @@ __device__ __forceinline__ double hs_storage_reward(const pgw_hs_params& p, cons
 // HSEVChargingEnv.step (ev_charging_env_hs.py:182-326); reset runs it with the
 // action-less default (:144, 185-187).  Vehicles in ascending index order, as
 // the reference's set iteration of small ints.
+template <class B, class Rec>
 __device__ __forceinline__ void hs_ev(const pgw_hs_params& p, const pgw_hs_step_info& s, int rescale,
-                                      bool reset, double a, int64_t n, int64_t e, const pgw_hs_buffers& b,
-                                      HSMeta& M, HSState& S, double& rp, double* ob, const HSRec& R) {
+                                      bool reset, double a, int64_t n, int64_t e, const B& b,
+                                      HSMeta& M, HSState& S, double& rp, double* ob, const Rec& R) {
+  using T = std::remove_pointer_t<decltype(B::ev_req)>;
   if (reset) a = 0.0;                                   // _action_space.low
   if (rescale) {
     oob_note(p.oob, oob_bad(a));
@@ -150,8 +175,8 @@ __device__ __forceinline__ void hs_ev(const pgw_hs_params& p, const pgw_hs_step_
   double demand = 0.0, consumed = 0.0, dsum = 0.0, unserved = 0.0;
   int nact = 0, dcnt = 0, ndep = 0;
   for (int v = 0; v < p.n_veh; ++v) {
-    double* rq = b.ev_req + (int64_t)v * n + e;
-    const double r = reset ? p.ev_req0[v] : *rq;
+    T* rq = b.ev_req + (int64_t)v * n + e;
+    const double r = reset ? p.ev_req0[v] : (double)*rq;
     const bool active = ((s.ev_window >> v) & 1ull) && (r > 0.0);
     double r_new = r;
     if (active) {
@@ -170,7 +195,7 @@ __device__ __forceinline__ void hs_ev(const pgw_hs_params& p, const pgw_hs_step_
       unserved = unserved + r;                          // departed (:260-263)
       ++ndep;
     }
-    *rq = r_new;
+    *rq = (T)r_new;
   }
   b.ev_charging[e] = now;
   double st[7];
@@ -224,9 +249,10 @@ __device__ __forceinline__ void hs_ev(const pgw_hs_params& p, const pgw_hs_step_
 // HSDevicesEnv.step (devices_env_hs.py:147-205).  Its draws on the resources
 // are made on kwargs AFTER the meta it returns was copied (:158-160), so they
 // never reach meta_state.
+template <class Rec>
 __device__ __forceinline__ void hs_devices(const pgw_hs_params& p, const pgw_hs_step_info& s, int rescale,
                                            bool reset, double a, const HSMeta& M, HSState& S, double& rp,
-                                           double* ob, const HSRec& R) {
+                                           double* ob, const Rec& R) {
 #pragma unroll
   for (int c = 0; c < PGW_HS_MAX_DEV; ++c) {
     if (c >= p.n_dev) break;
@@ -262,21 +288,26 @@ __device__ __forceinline__ void hs_devices(const pgw_hs_params& p, const pgw_hs_
   R.put(9, M.grid - gc);
 }
 
-__global__ void __launch_bounds__(kBlock) k_hs(pgw_hs_params p_, pgw_hs_step_info s, int64_t n,
-                                               pgw_hs_buffers b, const double* __restrict__ init_soc,
+// B: pgw_hs_buffers (T = double) or pgw_hs_buffers_f32 (T = float).  State is
+// widened on load, every store rounds once; min_voltage is fp64 for both (it
+// comes from the fp64 power flow) and ev_charging is a bit mask.
+template <class B>
+__global__ void __launch_bounds__(kBlock) k_hs(pgw_hs_params p_, pgw_hs_step_info s, int64_t n, B b,
+                                               const std::remove_pointer_t<decltype(B::soc)>* __restrict__ init_soc,
                                                int reset) {
+  using T = std::remove_pointer_t<decltype(B::soc)>;
   const pgw_hs_params& p = PGW_KERNARG0(pgw_hs_params);   // (no private copy)
   const int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   if (e >= n) return;
   HSMeta M;
-  M.pv = b.pv_power_last ? b.pv_power_last[e] : 0.0;   // meta_state carried over (None = NaN)
-  M.es = b.es_power_last[e];
+  M.pv = b.pv_power_last ? (double)b.pv_power_last[e] : 0.0;   // meta_state carried over (None = NaN)
+  M.es = (double)b.es_power_last[e];
   M.grid = p.max_grid_power;
   HSState S = {};
-  S.soc = reset ? clip(init_soc[e], p.soc_min, p.soc_max) : b.soc[e];
-  S.soc_cost = b.soc_cost[e];
-  S.ev_cost = b.ev_cost[e];
-  S.dev_cost = b.dev_cost[e];
+  S.soc = reset ? clip((double)init_soc[e], p.soc_min, p.soc_max) : (double)b.soc[e];
+  S.soc_cost = (double)b.soc_cost[e];
+  S.ev_cost = (double)b.ev_cost[e];
+  S.dev_cost = (double)b.dev_cost[e];
   double rp_storage = 0.0;
   // The chain is unrolled over its (at most 4) slots and every case stores its
   // own observations: with a loop over n_comp the per-slot arrays (S.rp, ob)
@@ -285,7 +316,7 @@ __global__ void __launch_bounds__(kBlock) k_hs(pgw_hs_params p_, pgw_hs_step_inf
   for (int c = 0; c < 4; ++c) {
     if (c >= p.n_comp) break;
     const double a = reset ? 0.0 : ld(b.action, e, c);
-    const HSRec R = {(!reset && b.step_meta) ? b.step_meta + (int64_t)c * PGW_HS_META_FIELDS * n : nullptr, n, e};
+    const HSRec<T> R = {(!reset && b.step_meta) ? b.step_meta + (int64_t)c * PGW_HS_META_FIELDS * n : nullptr, n, e};
     double ob[8];
     const int off = p.obs_off[c];
     S.rp[c] = 0.0;
@@ -322,10 +353,10 @@ __global__ void __launch_bounds__(kBlock) k_hs(pgw_hs_params p_, pgw_hs_step_inf
         break;
     }
   }
-  b.soc[e] = S.soc;
-  b.soc_cost[e] = S.soc_cost;
-  b.ev_cost[e] = S.ev_cost;
-  b.dev_cost[e] = S.dev_cost;
+  b.soc[e] = (T)S.soc;
+  b.soc_cost[e] = (T)S.soc_cost;
+  b.ev_cost[e] = (T)S.ev_cost;
+  b.dev_cost[e] = (T)S.dev_cost;
   if (reset) return;
   // base_hs.py:157-180: real power and the house reward, components in chain order
   double rp = 0.0, rew = 0.0;
@@ -339,18 +370,19 @@ __global__ void __launch_bounds__(kBlock) k_hs(pgw_hs_params p_, pgw_hs_step_inf
                    : k == PGW_HS_EV ? S.rew_ev : S.rew_dev;
     rew = rew + r;
   }
-  b.real_power[e] = rp;
-  b.reward[e] = rew;
-  b.es_power_last[e] = M.es;
-  if (b.pv_power_last) b.pv_power_last[e] = M.pv;
+  b.real_power[e] = (T)rp;
+  b.reward[e] = (T)rew;
+  b.es_power_last[e] = (T)M.es;
+  if (b.pv_power_last) b.pv_power_last[e] = (T)M.pv;
   if (b.meta_out) {
-    b.meta_out[e] = M.pv;
-    b.meta_out[n + e] = M.es;
-    b.meta_out[2 * n + e] = M.grid;
+    b.meta_out[e] = (T)M.pv;
+    b.meta_out[n + e] = (T)M.es;
+    b.meta_out[2 * n + e] = (T)M.grid;
   }
 }
 
-static int32_t hs_check(const pgw_hs_params* p, const pgw_hs_step_info* s, int64_t n, const pgw_hs_buffers& b) {
+template <class B>
+static int32_t hs_check(const pgw_hs_params* p, const pgw_hs_step_info* s, int64_t n, const B& b) {
   PGW_REQUIRE(p && s && n >= 0, "pgw_hs: null argument");
   PGW_REQUIRE(p->n_comp >= 1 && p->n_comp <= 4, "pgw_hs: bad n_comp");
   PGW_REQUIRE(p->n_veh >= 0 && p->n_veh <= PGW_HS_MAX_VEHICLES, "pgw_hs: bad n_veh");
@@ -369,6 +401,30 @@ static int32_t hs_check(const pgw_hs_params* p, const pgw_hs_step_info* s, int64
   return PGW_OK;
 }
 
+// The two entries, for either buffer struct.
+template <class B>
+static int32_t hs_reset(const pgw_hs_params* p, const pgw_hs_step_info* s, int64_t n,
+                        const std::remove_pointer_t<decltype(B::soc)>* init_soc, const B& b, void* stream) {
+  int32_t rc = hs_check(p, s, n, b);
+  if (rc) return rc;
+  PGW_REQUIRE(init_soc, "pgw_hs_reset: null init_soc");
+  if (n == 0) return PGW_OK;
+  hipLaunchKernelGGL(k_hs<B>, dim3(grid_for(n)), dim3(kBlock), 0, (hipStream_t)stream, *p, *s, n, b, init_soc, 1);
+  return check_launch("k_hs(reset)");
+}
+
+template <class B>
+static int32_t hs_step(const pgw_hs_params* p, const pgw_hs_step_info* s, int64_t n, const B& b, void* stream) {
+  using T = std::remove_pointer_t<decltype(B::soc)>;
+  int32_t rc = hs_check(p, s, n, b);
+  if (rc) return rc;
+  PGW_REQUIRE(b.action.ptr && b.reward && b.real_power, "pgw_hs_step: null buffer");
+  if (n == 0) return PGW_OK;
+  hipLaunchKernelGGL(k_hs<B>, dim3(grid_for(n)), dim3(kBlock), 0, (hipStream_t)stream, *p, *s, n, b,
+                     (const T*)nullptr, 0);
+  return check_launch("k_hs(step)");
+}
+
 }  // namespace pgw
 
 using namespace pgw;
@@ -377,23 +433,22 @@ extern "C" {
 
 int32_t pgw_hs_reset(const pgw_hs_params* p, const pgw_hs_step_info* s, int64_t n, const double* init_soc,
                      pgw_hs_buffers b, void* stream) {
-  int32_t rc = hs_check(p, s, n, b);
-  if (rc) return rc;
-  PGW_REQUIRE(init_soc, "pgw_hs_reset: null init_soc");
-  if (n == 0) return PGW_OK;
-  hipLaunchKernelGGL(k_hs, dim3(grid_for(n)), dim3(kBlock), 0, (hipStream_t)stream, *p, *s, n, b, init_soc, 1);
-  return check_launch("k_hs(reset)");
+  return hs_reset(p, s, n, init_soc, b, stream);
 }
 
 int32_t pgw_hs_step(const pgw_hs_params* p, const pgw_hs_step_info* s, int64_t n, pgw_hs_buffers b,
                     void* stream) {
-  int32_t rc = hs_check(p, s, n, b);
-  if (rc) return rc;
-  PGW_REQUIRE(b.action.ptr && b.reward && b.real_power, "pgw_hs_step: null buffer");
-  if (n == 0) return PGW_OK;
-  hipLaunchKernelGGL(k_hs, dim3(grid_for(n)), dim3(kBlock), 0, (hipStream_t)stream, *p, *s, n, b,
-                     (const double*)nullptr, 0);
-  return check_launch("k_hs(step)");
+  return hs_step(p, s, n, b, stream);
+}
+
+int32_t pgw_hs_reset_f32(const pgw_hs_params* p, const pgw_hs_step_info* s, int64_t n, const float* init_soc,
+                         pgw_hs_buffers_f32 b, void* stream) {
+  return hs_reset(p, s, n, init_soc, b, stream);
+}
+
+int32_t pgw_hs_step_f32(const pgw_hs_params* p, const pgw_hs_step_info* s, int64_t n, pgw_hs_buffers_f32 b,
+                        void* stream) {
+  return hs_step(p, s, n, b, stream);
 }
 
 }  // extern "C"

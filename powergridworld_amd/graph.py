@@ -154,9 +154,10 @@ class StepGraph:
 
     # ------------------------------------------------------------ HS house
     def _init_hs(self, env, actions, kwargs):
-        """pgw_hs_step captured per episode position: the house's per-step
-        values (PV / device rows, grid cost, EV times and window) come from
-        _info_at(k), as the eager step builds them at k."""
+        """pgw_hs_step (the fp32 house: pgw_hs_step_f32) captured per episode
+        position: the house's per-step values (PV / device rows, grid cost, EV
+        times and window) come from _info_at(k), as the eager step builds them
+        at k.  Actions are packed tensors of the house's dtype."""
         if kwargs_given(kwargs):
             raise ValueError("capture_step: the house's observation inputs are bound at its first step")
         if env.params.pv_grid_aware and env._mv_state is None:
@@ -171,11 +172,11 @@ class StepGraph:
         sets = []
         for a in actions:
             if not isinstance(a, torch.Tensor) or tuple(a.shape) != (n, len(env.envs)) or \
-                    a.dtype != torch.float64 or a.device != torch.device(env.device):
-                raise ValueError("capture_step: house actions must be packed [%d, %d] float64 tensors on %s"
-                                 % (n, len(env.envs), env.device))
+                    a.dtype != env.dtype or a.device != torch.device(env.device):
+                raise ValueError("capture_step: house actions must be packed [%d, %d] %s tensors on %s"
+                                 % (n, len(env.envs), str(env.dtype).replace("torch.", ""), env.device))
             b = type(env._bufs).from_buffer_copy(env._bufs)
-            b.action = _lib.Mat(a.data_ptr(), a.stride(0), a.stride(1))
+            b.action = env._mat_cls(a.data_ptr(), a.stride(0), a.stride(1))
             if env.params.pv_grid_aware:
                 b.min_voltage = env._mv_state.data_ptr()
             sets.append(b)
@@ -189,7 +190,7 @@ class StepGraph:
         if g is None:
             env = self.env
             infos = [env._info_at(k + i) for i in range(self.steps)]
-            fn = _lib.lib().pgw_hs_step
+            fn = env._fn_step
 
             def launch():
                 st = env._stream()

@@ -14,7 +14,8 @@ on the generic path, fused=False; HETF: HET with fp32 storage
 C3 with fp32 storage (pgw_mc_agent_step_f32); C3L: C3 at
 65 536 envs; C2Gk / C3Gk: the step replayed from captured hipGraphs of k steps,
 C3 through the device clocks; C3Pk / HSPk: captured once per episode position,
-powergridworld_amd/graph.py)
+powergridworld_amd/graph.py; HS32 / HS32P8: HS / HSP8 with fp32 storage
+(pgw_hs_step_f32))
 """
 import argparse
 import json
@@ -184,12 +185,13 @@ def bench_het(dev, steps, warmup, n=65536, pool=16, fused="auto", conv="opendss"
                 batch=n, agents=3, steps=steps, seconds=dt)
 
 
-def bench_hs(dev, steps, warmup, n=65536, pool=16, graph=0):
+def bench_hs(dev, steps, warmup, n=65536, pool=16, graph=0, dtype=torch.float64):
     from powergridworld_amd.base_hs import HSMultiComponentEnv
     from powergridworld_amd.scenarios.heterogeneous_hs import make_env_config
-    env = HSMultiComponentEnv(**make_env_config(), num_envs=n, device=dev)
+    env = HSMultiComponentEnv(**make_env_config(), num_envs=n, device=dev, dtype=dtype)
     gen = torch.Generator(dev).manual_seed(0)
     acts = torch.empty((pool, n, len(env.envs)), dtype=torch.float64, device=dev).uniform_(-1, 1, generator=gen)
+    acts = acts.to(dtype)          # (the same draws for both storage dtypes)
     k = [0]
 
     def step():
@@ -211,8 +213,10 @@ def bench_hs(dev, steps, warmup, n=65536, pool=16, graph=0):
         steps, warmup = steps // graph, max(warmup // graph, (pool // graph) * (L // graph + 1))
     dt = timed_loop(env, step, env.reset, steps, warmup)
     steps *= max(graph, 1)
-    return dict(config="HS" + ("P%d" % graph if graph else ""),
+    f32 = dtype == torch.float32
+    return dict(config="HS" + ("32" if f32 else "") + ("P%d" % graph if graph else ""),
                 workload="Home-Steward house (PV, battery, EV, devices; shipped JSON scenario)" + (
+                    ", fp32 storage (pgw_hs_step_f32)" if f32 else "") + (
                     ", %d-step captured graphs per episode position" % graph if graph else ""),
                 batch=n, agents=1, steps=steps, seconds=dt)
 
@@ -240,7 +244,9 @@ def main():
            "C3L": lambda *a: bench_c3(*a, n=65536),
            "C3F": lambda *a: bench_c3(*a, dtype=torch.float32),
            "C3G8F": lambda *a: bench_c3(*a, graph=8, dtype=torch.float32),
-           "HSP8": lambda *a: bench_hs(*a, graph=8)}
+           "HSP8": lambda *a: bench_hs(*a, graph=8),
+           "HS32": lambda *a: bench_hs(*a, dtype=torch.float32),
+           "HS32P8": lambda *a: bench_hs(*a, graph=8, dtype=torch.float32)}
     for name in args.configs.split(","):
         r = fns[name](dev, args.steps, args.warmup)
         units = r["batch"] * r["agents"] * r["steps"]
