@@ -605,11 +605,14 @@ class Feeder:
                     abs(V[sensed(q)]) < abs(V[sensed(p)])
                 p = q if better else p
             a, b = self._reg_nodes(t, p)
-            vc = V[sensed(p)] / c["ptratio"]
+            # V / PTratio: each part divided by the real ratio (pgw.h "V / ptratio"; NumPy's
+            # complex / real multiplies by the rounded reciprocal instead, an ulp off)
+            pt = lambda v: complex(v.real / c["ptratio"], v.imag / c["ptratio"])
+            vc = pt(V[sensed(p)])
             vlocal = 0.0
             if c["vlimit"] > 0:
                 a0, b0 = self._reg_nodes(t, 0)
-                vlocal = abs(V[a0 if c["winding"] == 1 else b0] / c["ptratio"]) if c["bus"] else abs(vc)
+                vlocal = abs(pt(V[a0 if c["winding"] == 1 else b0])) if c["bus"] else abs(vc)
             if not c["bus"] and (c["R"] != 0.0 or c["X"] != 0.0):
                 tp = [w.get("tap", 1.0) for w in t["windings"]]
                 tp[c["winding"] - 1] = taps[g]

@@ -468,6 +468,31 @@ def matf(t2d):
     return Matf(t2d.data_ptr(), t2d.stride(0), t2d.stride(1))
 
 
+def reg_params(reg, S_ptr, rho_ptr):
+    """pgw_reg_params of a Feeder.regulators() model; S_ptr / rho_ptr: the device
+    copies of reg["S"] (r x r complex, row-major) and reg["rho"] (r)."""
+    r = len(reg["nodes"])
+    rp = RegParams()
+    rp.n_reg, rp.r_reg = -(-r // 8) * 8, r
+    rp.n_phase, rp.n_ctrl = len(reg["phases"]), len(reg["ctrls"])
+    for q, ph in enumerate(reg["phases"]):
+        d = rp.phase[q]
+        d.a, d.b, d.ctrl, d.tap_winding = ph["a"], ph["b"], ph["ctrl"], ph["tap_winding"]
+        for key in ("A", "B", "C"):
+            getattr(d, key)[0], getattr(d, key)[1] = ph[key].real, ph[key].imag
+        d.tap1, d.tap2 = ph["tap1"], ph["tap2"]
+    for g, c in enumerate(reg["ctrls"]):
+        d = rp.ctrl[g]
+        for key in ("n_mon", "pick", "winding", "max_tap_change", "ldc", "vlim_node", "inverse_time", "vreg",
+                    "band", "ptratio", "ctprim", "r_ldc", "x_ldc", "vbase", "incr", "min_tap", "max_tap",
+                    "delay", "vlimit"):
+            setattr(d, key, c[key])
+        for i in range(c["n_mon"]):
+            d.mon_node[i], d.mon_phase[i] = c["mon_node"][i], c["mon_phase"][i]
+    rp.S, rp.rho = S_ptr, rho_ptr
+    return rp
+
+
 STORAGE_DTYPES = (torch.float64, torch.float32)
 
 

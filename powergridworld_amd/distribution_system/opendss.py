@@ -1360,7 +1360,7 @@ class OpenDSSSolver(PowerFlowSolver):
 
     def _init_regulators(self):
         reg, n, dev = self.regulators, self.num_envs, self.device
-        r, nc = len(reg["nodes"]), len(reg["ctrls"])
+        r = len(reg["nodes"])
         self.reg_taps = torch.tensor(np.repeat(reg["taps0"][:, None], n, 1), dtype=torch.float64, device=dev)
         # K per env, its upper triangle (pgw_pfg_tables.Kreg); DSS taps: K = 0
         self._Kreg = torch.zeros((r * (r + 1) // 2, n, 2), dtype=torch.float64, device=dev)
@@ -1370,25 +1370,7 @@ class OpenDSSSolver(PowerFlowSolver):
         self._reg_nchg = torch.zeros(1, dtype=torch.int32, device=dev)
         self._reg_S = torch.tensor(np.ascontiguousarray(reg["S"]).view(np.float64).ravel(), device=dev)
         self._reg_rho = torch.tensor(reg["rho"], dtype=torch.float64, device=dev)
-        rp = _lib.RegParams()
-        rp.n_reg, rp.r_reg = -(-r // 8) * 8, r
-        rp.n_phase, rp.n_ctrl = len(reg["phases"]), nc
-        for q, ph in enumerate(reg["phases"]):
-            d = rp.phase[q]
-            d.a, d.b, d.ctrl, d.tap_winding = ph["a"], ph["b"], ph["ctrl"], ph["tap_winding"]
-            for key in ("A", "B", "C"):
-                getattr(d, key)[0], getattr(d, key)[1] = ph[key].real, ph[key].imag
-            d.tap1, d.tap2 = ph["tap1"], ph["tap2"]
-        for g, c in enumerate(reg["ctrls"]):
-            d = rp.ctrl[g]
-            for key in ("n_mon", "pick", "winding", "max_tap_change", "ldc", "vlim_node", "inverse_time", "vreg",
-                        "band", "ptratio", "ctprim", "r_ldc", "x_ldc", "vbase", "incr", "min_tap", "max_tap",
-                        "delay", "vlimit"):
-                setattr(d, key, c[key])
-            for i in range(c["n_mon"]):
-                d.mon_node[i], d.mon_phase[i] = c["mon_node"][i], c["mon_phase"][i]
-        rp.S, rp.rho = self._reg_S.data_ptr(), self._reg_rho.data_ptr()
-        self._reg_params = rp
+        self._reg_params = _lib.reg_params(reg, self._reg_S.data_ptr(), self._reg_rho.data_ptr())
         self.control_iterations = 0
 
     def set_regulator_taps(self, taps):

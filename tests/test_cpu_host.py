@@ -521,6 +521,69 @@ def test_regcontrol_sample_options_model():
     assert not moved
 
 
+REGCTL_W1 = os.path.join(REPO, "tests", "data", "regctl_w1_feeder.dss")
+
+
+def test_regcontrol_winding_1_model():
+    """RegControls on winding 1 (tests/data/regctl_w1_feeder.dss: regctl2's
+    regulators turned round, winding=1 or omitted -- OpenDSS's default):
+    every regulated phase taps winding 1 and every control monitors it, the
+    initial taps are winding 1's DSS taps, the sensed and Vlimit nodes are
+    winding-1 terminals (or the regulated bus's); the Woodbury model gives
+    the rebuilt network's voltages; the oracle's loop from the DSS taps ends
+    in band or at a tap limit.  Parity unpinned (no OpenDSS)."""
+    from oracle.pf_oracle import Feeder as OracleFeeder
+    from powergridworld_amd.distribution_system.feeder import Feeder, load_feeder_spec
+    spec = load_feeder_spec(REGCTL_W1)
+    rc = {r_["name"]: dict(r_["props"]) for r_ in spec["regcontrols"]}
+    assert "winding" not in rc["reg3"] and all(rc[k]["winding"] == "1" for k in rc if k != "reg3")
+    f, o = Feeder(spec), OracleFeeder(spec)
+    reg = f.regulators()
+    R = reg["nodes"]
+    name = lambda j: f.node_names[R[j]]
+    c = {d["name"]: d for d in reg["ctrls"]}
+    assert len(reg["phases"]) == 9 and len(R) == 21 and len(c) == 5
+    assert all(ph["tap_winding"] == 1 for ph in reg["phases"]) and all(d["winding"] == 1 for d in c.values())
+    assert all(cc["winding"] == 1 for _, cc in o.reg_controls())
+    np.testing.assert_array_equal(reg["taps0"], [1.0, 1.0125, 0.99375, 1.0, 1.0])
+    np.testing.assert_array_equal([ph["tap1"] for ph in reg["phases"][:3]], [1.0, 1.0125, 0.99375])
+    assert all(ph["tap2"] == 1.0 for ph in reg["phases"])
+    # a = the winding-1 (load-side) terminal, b = winding 2's
+    assert [(name(ph["a"]), name(ph["b"])) for ph in reg["phases"][:4]] == \
+        [("rg60.1", "650.1"), ("rg60.2", "650.2"), ("rg60.3", "650.3"), ("b5.1", "b3.1")]
+    assert [name(j) for j in c["reg1"]["mon_node"]] == ["b3.1"] and name(c["reg1"]["vlim_node"]) == "rg60.1"
+    assert [name(j) for j in c["reg2"]["mon_node"]] == ["rg60.2"] and c["reg2"]["vlim_node"] == -1
+    assert c["reg2"]["ldc"] == 1
+    assert [name(j) for j in c["reg3"]["mon_node"]] == ["rg60.3"]
+    assert [name(j) for j in c["regg"]["mon_node"]] == ["b5.1", "b5.2", "b5.3"] and c["regg"]["ldc"] == 1
+    assert [name(j) for j in c["regh"]["mon_node"]] == ["b8.1", "b8.2", "b8.3"]
+    assert name(c["regh"]["vlim_node"]) == "b7.1"
+    r = len(R)
+    rng = np.random.default_rng(2)
+    for _ in range(3):
+        taps = reg["taps0"] + 0.00625 * rng.integers(-8, 9, size=len(reg["ctrls"]))
+        D = np.zeros((r, r), complex)
+        for ph in reg["phases"]:
+            t = taps[ph["ctrl"]]
+            t1 = t if ph["tap_winding"] == 1 else ph["tap1"]
+            t2 = t if ph["tap_winding"] == 2 else ph["tap2"]
+            Y = lambda a, b: np.array([[ph["A"] / a ** 2, ph["B"] / (a * b)], [ph["B"] / (a * b), ph["C"] / b ** 2]])
+            D[np.ix_([ph["a"], ph["b"]], [ph["a"], ph["b"]])] += Y(t1, t2) - Y(ph["tap1"], ph["tap2"])
+        K = np.linalg.solve(np.eye(r) + D @ reg["S"], D)
+        V = f.V0 - f.Z[:, R] @ (K @ f.V0[R])
+        ot = o.with_taps(list(taps))
+        np.testing.assert_allclose(V, ot.V0, rtol=1e-9, atol=1e-9 * np.abs(ot.V0).max())
+    kw = np.array([ld["kw"] for ld in spec["loads"]], float)
+    kvar = np.array([ld["kvar"] for ld in spec["loads"]], float)
+    for scale in (0.5, 1.0):                       # (at full load Reg1 ends on its top tap)
+        V, it, tp, cp = o.solve_regulated(scale * kw[None], scale * kvar[None], reg["taps0"][None])
+        assert 2 <= cp[0] < 15 and (tp[0] != reg["taps0"]).any()
+        # no control acts any more: each is in band, or its move is clamped away at a tap limit
+        _, moved = o.reg_control_pass(V[0], list(tp[0]))
+        assert not moved
+    assert tp[0][0] == 1.1
+
+
 def test_regcontrol_options_oracle_semantics():
     """The oracle's Sample options on regctl2_feeder.dss, from chosen taps:
     Vlimit forces Reg2 down while its local voltage is above the limit

@@ -25,6 +25,7 @@ MODELS = os.path.join(HERE, "data", "models_feeder.dss")
 XFMR3 = os.path.join(HERE, "data", "xfmr3_feeder.dss")
 REGCTL = os.path.join(HERE, "data", "regctl_feeder.dss")
 REGCTL2 = os.path.join(HERE, "data", "regctl2_feeder.dss")
+REGCTL_W1 = os.path.join(HERE, "data", "regctl_w1_feeder.dss")
 IEEE13 = "ieee_13_dss/IEEE13Nodeckt.dss"
 SHAPE = "ieee_13_dss/annual_hourly_load_profile.csv"
 
@@ -258,27 +259,14 @@ def test_three_winding_and_centre_tap_transformers_vs_oracle():
     np.testing.assert_allclose(g2, o2, rtol=1e-9, atol=0)
 
 
-@pytest.mark.parametrize("feeder", ["regctl", "regctl2"])
-@pytest.mark.parametrize("semantics", ["exact", "opendss"])
-def test_regcontrol_vs_oracle(semantics, feeder):
-    """RegControl (tests/data/regctl_feeder.dss: three single-phase regulators,
-    one with line-drop compensation, and a gang-operated 3-phase one;
-    regctl2_feeder.dss: Sample's options -- a remote regulated bus, Vlimit
-    over line-drop compensation, inverse time, PTphase=max / min): per-env
-    taps through the Woodbury-corrected general kernel and the device control
-    pass (pgw_reg_control / pgw_reg_factor) against the oracle's SolveSnap
-    restatement that rebuilds and re-inverts Y at every tap set -- the same
-    final taps in every env (exactly), every node within 1e-9 rel, over two
-    consecutive steps (taps persist) from random per-env starting taps.
-    Parity unpinned (no OpenDSS)."""
-    K = 192
-    path = {"regctl": REGCTL, "regctl2": REGCTL2}[feeder]
+def _regcontrol_vs_oracle(semantics, feeder, K):
+    path = {"regctl": REGCTL, "regctl2": REGCTL2, "regctl_w1": REGCTL_W1}[feeder]
     o = _oracle(path, 1.0)
     s = _solver(path, num_envs=K, convergence=semantics)
     f = o.feeder
     reg = s.regulators
     nc = len(reg["ctrls"])
-    assert s.general and reg is not None and nc == {"regctl": 4, "regctl2": 5}[feeder]
+    assert s.general and reg is not None and nc == {"regctl": 4, "regctl2": 5, "regctl_w1": 5}[feeder]
     rng = np.random.default_rng(11)
     taps = reg["taps0"][None, :] + 0.00625 * rng.integers(-6, 7, size=(K, nc))
     s.set_regulator_taps(torch.tensor(taps.T.copy(), device=DEV))
@@ -305,6 +293,32 @@ def test_regcontrol_vs_oracle(semantics, feeder):
         moved += int((tp != taps).any(1).sum())
         taps = tp
     assert moved > K // 4
+
+
+@pytest.mark.parametrize("feeder", ["regctl", "regctl2", "regctl_w1"])
+@pytest.mark.parametrize("semantics", ["exact", "opendss"])
+def test_regcontrol_vs_oracle(semantics, feeder):
+    """RegControl (tests/data/regctl_feeder.dss: three single-phase regulators,
+    one with line-drop compensation, and a gang-operated 3-phase one;
+    regctl2_feeder.dss: Sample's options -- a remote regulated bus, Vlimit
+    over line-drop compensation, inverse time, PTphase=max / min;
+    regctl_w1_feeder.dss: the same options with every control on winding 1,
+    OpenDSS's default): per-env taps through the Woodbury-corrected general
+    kernel and the device control pass (pgw_reg_control / pgw_reg_factor)
+    against the oracle's SolveSnap
+    restatement that rebuilds and re-inverts Y at every tap set -- the same
+    final taps in every env (exactly), every node within 1e-9 rel, over two
+    consecutive steps (taps persist) from random per-env starting taps.
+    Parity unpinned (no OpenDSS)."""
+    _regcontrol_vs_oracle(semantics, feeder, 96 if feeder == "regctl_w1" else 192)
+
+
+@pytest.mark.parametrize("semantics", ["exact", "opendss"])
+def test_regcontrol_odd_batch_vs_oracle(semantics):
+    """test_regcontrol_vs_oracle on regctl_feeder.dss (12 regulator nodes: the
+    factor kernel's two-envs-per-block instance) at an odd batch, whose last
+    block holds one env only."""
+    _regcontrol_vs_oracle(semantics, "regctl", 65)
 
 
 def test_general_kernel_extrema_and_output_subset():
