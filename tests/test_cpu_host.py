@@ -321,6 +321,61 @@ def test_ma_step_argument_checks():
 MODELS = os.path.join(REPO, "tests", "data", "models_feeder.dss")
 
 
+def _law_branch(ld, vk):
+    """The branch of a load's law at vk pu, by the load's own thresholds."""
+    if ld["model"] == 8:
+        return "off" if vk < ld["zipv"][6] else "in"
+    if vk <= ld.get("vlowpu", 0.5):
+        return "low"
+    if vk <= ld.get("vminpu", 0.95):
+        return "under"
+    return "over" if vk > ld.get("vmaxpu", 1.05) else "in"
+
+
+def _expected_power(ld, vk, P, Q):
+    """(P, Q) a load phase element of nominal (P, Q) draws at vk pu (OpenDSS's
+    load models as oracle/pf_oracle.py's docstring lists them): at or below
+    Vlowpu the nominal admittance; the constant-power part P (v / vmin)^2 below
+    Vminpu and P (v / vmax)^2 above Vmaxpu; ZIP off below its cutoff."""
+    md, br = ld["model"], _law_branch(ld, vk)
+    if br == "off":
+        return 0.0, 0.0
+    if br == "low":
+        return P * vk ** 2, Q * vk ** 2
+    vc = {"under": ld.get("vminpu", 0.95), "in": vk, "over": ld.get("vmaxpu", 1.05)}[br]
+    band = (vk / vc) ** 2
+    if md == 1:
+        return P * band, Q * band
+    if md in (3, 7):
+        return P * band, Q * vk ** 2
+    if md == 4:
+        return P * vk ** ld["cvrwatts"], Q * vk ** ld["cvrvars"]
+    if md == 5:
+        return P * vk, Q * vk
+    if md == 6:
+        return P * band, Q
+    z = ld["zipv"]
+    return P * (z[0] * vk ** 2 + z[1] * vk + z[2]), Q * (z[3] * vk ** 2 + z[4] * vk + z[5])
+
+
+def _assert_element_powers(spec, o, S, v, W_ph, var_ph, skip=None):
+    """Every element draws what its model's law gives at its voltage, in band
+    and out of it.  S, v, W_ph, var_ph: [m] or [K, m]; skip [K, m]: samples on
+    a threshold's knife edge.  Returns the branch names, as v's shape."""
+    S, v, W_ph, var_ph = (np.atleast_2d(a) for a in (S, v, W_ph, var_ph))
+    br = np.empty(v.shape, dtype=object)
+    for k, li in enumerate(o.elem_load):
+        ld = spec["loads"][li]
+        for e in range(v.shape[0]):
+            br[e, k] = _law_branch(ld, v[e, k])
+            if skip is not None and skip[e, k]:
+                continue
+            exp = _expected_power(ld, v[e, k], W_ph[e, k], var_ph[e, k])
+            np.testing.assert_allclose([S[e, k].real, S[e, k].imag], exp, rtol=1e-9, atol=1e-9 * abs(W_ph[e, k]),
+                                       err_msg="%s env %d v %.6f %s" % (ld["name"], e, v[e, k], br[e, k]))
+    return br
+
+
 def test_dss_load_models_and_series_capacitor():
     """OpenDSS load models 1-8 and a series capacitor (tests/data/models_feeder.dss).
     Parity unpinned (no OpenDSS): the native build equals the oracle's
@@ -353,21 +408,109 @@ def test_dss_load_models_and_series_capacitor():
     assert resid < 1e-8
     S = U * np.conj(I)
     v = np.abs(U) / o.elem_vbase
-    for k, li in enumerate(o.elem_load):
-        ld = spec["loads"][li]
-        md, vk = ld["model"], v[k]
-        assert 0.9 < vk <= 1.05, (ld["name"], vk)
-        P, Q = W_ph[k], var_ph[k]
-        exp = {1: (P, Q), 3: (P, Q * vk ** 2), 4: (P * vk ** ld["cvrwatts"], Q * vk ** ld["cvrvars"]),
-               5: (P * vk, Q * vk), 6: (P, Q), 7: (P, Q * vk ** 2)}
-        if md == 8:
-            z = ld["zipv"]
-            exp[8] = (P * (z[0] * vk ** 2 + z[1] * vk + z[2]), Q * (z[3] * vk ** 2 + z[4] * vk + z[5]))
-        if md in (1, 3, 6, 7) and vk <= 0.95:      # below Vminpu the constant-P part is constant Z
-            continue
-        np.testing.assert_allclose([S[k].real, S[k].imag], exp[md], rtol=1e-9, err_msg=ld["name"])
+    assert ((0.9 < v) & (v <= 1.05)).all(), v
+    _assert_element_powers(spec, o, S, v, W_ph, var_ph)
     i = f.node_index
     assert all(abs(V[0][o.idx["b.%d" % p]]) > abs(V[0][o.idx["a.%d" % p]]) for p in (1, 2, 3))
+
+
+BANDS = os.path.join(REPO, "tests", "data", "models_bands_feeder.dss")
+BANDS_SPEC = {   # load: (model, Vlowpu, Vminpu, Vmaxpu, ZIPV cutoff or None), as the fixture's text has them
+    "pq1": (1, 0.5, 0.95, 1.05, None), "pq2": (1, 0.976, 0.985, 0.993, None), "m3": (3, 0.975, 0.992, 0.998, None),
+    "m4": (4, 0.95, 0.97, 1.0, None), "m5": (5, 0.945, 0.965, 1.005, None), "m6": (6, 0.96, 0.99, 1.0, None),
+    "m7": (7, 0.94, 0.97, 1.01, None), "m8": (8, 0.5, 0.95, 1.05, 0.97)}
+
+
+@pytest.mark.parametrize("convergence", ["exact", "opendss"])
+def test_per_load_bands_reach_the_element_records(convergence):
+    """tests/data/models_bands_feeder.dss: the parser and feeder.py carry each
+    load's own Vlowpu / Vminpu / Vmaxpu, CVR exponents and ZIPV into the
+    pgw_pfg_elem records the general kernel reads (OpenDSSSolver._general_elems
+    on the host-side feeder: no GPU), padded elements included."""
+    import types
+    from powergridworld_amd.distribution_system.feeder import Feeder, load_feeder_spec
+    from powergridworld_amd.distribution_system.opendss import OpenDSSSolver
+    spec = load_feeder_spec(BANDS)
+    by_name = {ld["name"]: ld for ld in spec["loads"]}
+    for name, (md, lo, mn, mx, cut) in BANDS_SPEC.items():
+        ld = by_name[name]
+        assert (ld["model"], ld["vlowpu"], ld["vminpu"], ld["vmaxpu"]) == (md, lo, mn, mx), name
+        assert (ld["zipv"][6] if ld.get("zipv") else None) == cut, name
+    f = Feeder(spec)
+    M = 24                                                   # 16 real elements and a padded chunk
+    assert f.m == 16
+    stub = types.SimpleNamespace(feeder=f, M=M, convergence=convergence, _ctrl_names=["pq1", "pq2"])
+    el = OpenDSSSolver._general_elems(stub)
+    assert len(el) == M
+    seen = set()
+    for k in range(f.m):
+        ld = spec["loads"][f.elem_load[k]]
+        md, lo, mn, mx, cut = BANDS_SPEC[ld["name"]]
+        seen.add(ld["name"])
+        e = el[k]
+        assert (e.model, e.vlo2, e.vmn2, e.vmx2) == (md, lo ** 2, mn ** 2, mx ** 2), (k, ld["name"])
+        assert (e.base_kw, e.base_kvar, e.nph) == (ld["kw"], ld["kvar"], ld["phases"])
+        assert (e.exp_p, e.exp_q) == ((0.8, 3.0) if md == 4 else (1.0, 2.0))
+        assert e.ctrl == {"pq1": 0, "pq2": 1}.get(ld["name"], -1)
+        if md == 8:
+            assert list(e.zip) == [0.3, 0.3, 0.4, 0.5, 0.2, 0.3] and e.vcut2 == cut ** 2
+        if convergence == "opendss":
+            assert (e.y0r, e.y0i) == (ld["kw"] * 1000.0 / ld["phases"], -(ld["kvar"] * 1000.0 / ld["phases"]))
+        else:
+            assert (e.y0r, e.y0i) == (0.0, 0.0)
+    assert seen == set(BANDS_SPEC)
+    # no two loads share a band: a record read from the wrong element would show
+    assert len({BANDS_SPEC[n][1:4] for n in BANDS_SPEC}) == len(BANDS_SPEC) - 1    # (pq1 and m8: the defaults)
+    for k in range(f.m, M):
+        e = el[k]
+        assert (e.model, e.ctrl, e.base_kw, e.base_kvar, e.y0r, e.y0i) == (1, -1, 0.0, 0.0, 0.0, 0.0)
+        assert (e.vlo2, e.vmn2, e.vmx2) == (0.25, 0.9025, 1.1025)
+
+
+@pytest.mark.parametrize("semantics", ["exact", "opendss"])
+def test_bands_ladder_reaches_every_branch_of_every_load(semantics):
+    """The ladder of tests/_pfg_direct_common.py on the oracle: every (load,
+    branch) cell holds at least 2 % of that load's (env, phase) samples; at
+    most 1 % of the envs sit on a knife edge (an element within 1e-9 rel of
+    its load's Vlowpu or ZIPV cutoff, or a tested change within 1e-6 rel of
+    tol); every converged env's elements draw the power their law gives at
+    their voltage, out of band included.  A load that jumps at Vlowpu or at its
+    cutoff has no solution where its own voltage change crosses the threshold:
+    those envs cycle and stop at the cap (counted, at most 8 %)."""
+    from tests import _pfg_direct_common as C
+    r = C.bands_oracle(semantics)
+    o = r["oracle"]
+    f, spec = o.feeder, o.feeder.spec
+    K = C.BANDS_K
+    V, it, conv = r["V"], r["it"], r["converged"]
+    assert (~conv).sum() <= 0.08 * K, (~conv).sum()
+    if semantics == "exact":
+        assert it[conv].max() <= 25 < C.BANDS_EXACT_MAX_ITER
+    else:
+        assert it[conv].min() >= 2 and (it[~conv] == 15).all()
+    U = V @ f.Cinc.T
+    v = np.abs(U) / f.elem_vbase
+    thr = np.array([(spec["loads"][li]["zipv"][6] if spec["loads"][li]["model"] == 8
+                     else spec["loads"][li].get("vlowpu", 0.5)) for li in f.elem_load])
+    knife = np.abs(v / thr - 1.0) < 1e-9
+    assert (knife.any(1) | r["near_tol"]).sum() <= 0.01 * K
+    W_ph = r["kw"][:, f.elem_load] * 1000.0 / f.elem_nph
+    var_ph = r["kvar"][:, f.elem_load] * 1000.0 / f.elem_nph
+    br = np.empty(v.shape, dtype=object)
+    for k, li in enumerate(f.elem_load):
+        br[:, k] = [_law_branch(spec["loads"][li], x) for x in v[:, k]]
+    for li, ld in enumerate(spec["loads"]):
+        el = np.nonzero(f.elem_load == li)[0]
+        if ld["name"] == "pq1" or len(el) == 0:          # the controllable load keeps the default band
+            continue
+        for name in (("off", "in") if ld["model"] == 8 else ("low", "under", "in", "over")):
+            share = (br[:, el] == name).mean()
+            assert share >= 0.02, (ld["name"], name, share)
+    if semantics == "exact":
+        # the fixed point's powers (a stopped iterate's voltages are one pass ahead of its currents)
+        sub = np.nonzero(conv)[0][::7]
+        I = f.load_currents(U[sub], W_ph[sub], var_ph[sub])
+        _assert_element_powers(spec, f, U[sub] * np.conj(I), v[sub], W_ph[sub], var_ph[sub], skip=knife[sub])
 
 
 XFMR3 = os.path.join(REPO, "tests", "data", "xfmr3_feeder.dss")

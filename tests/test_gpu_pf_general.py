@@ -240,6 +240,43 @@ def test_load_models_and_series_capacitor_vs_oracle():
     np.testing.assert_allclose(g2, o2, rtol=1e-9, atol=0)
 
 
+@pytest.mark.parametrize("semantics", ["exact", "opendss"])
+def test_per_load_bands_ladder_vs_oracle(semantics):
+    """Bands that differ per load (tests/data/models_bands_feeder.dss): a
+    ladder of 1000 shuffled envs on PQ1 (tests/_pfg_direct_common.py) takes
+    every load through every branch of its law -- below Vlowpu, below Vminpu,
+    above Vmaxpu, under the ZIPV cutoff (tests/test_cpu_host.py shows it on the
+    oracle) -- through the solver against the oracle: every node within 1e-9
+    rel, the same iteration count for every env, and the sign of `iterations`
+    equal to the oracle's convergence (envs whose load jumps at a threshold
+    cycle and stop at the cap).  Knife-edge envs (at most 1 %) are left out."""
+    from tests import _pfg_direct_common as C
+    r = C.bands_oracle(semantics)
+    f = r["oracle"].feeder
+    K = C.BANDS_K
+    kw = dict(max_iter=C.BANDS_EXACT_MAX_ITER, tol=C.BANDS_EXACT_TOL) if semantics == "exact" else {}
+    s = _solver(C.bands_path(), system_load_rescale_factor=C.BANDS_RESCALE, num_envs=K, convergence=semantics, **kw)
+    assert s.general and s.feeder.m == 16 and (s.feeder.elem_model != 1).any()
+    s.calculate_power_flow({C.BANDS_CTRL: torch.tensor(C.bands_ladder(), device=DEV)}, None,
+                           current_time=pd.Timestamp(C.BANDS_TIME))
+    torch.cuda.synchronize()
+    bv = s.get_bus_voltages()
+    g = np.stack([bv[nm].cpu().numpy() for nm in f.node_names], 1)
+    git = s.iterations.cpu().numpy()
+    U = r["V"] @ f.Cinc.T
+    v = np.abs(U) / f.elem_vbase
+    spec = f.spec
+    thr = np.array([(spec["loads"][li]["zipv"][6] if spec["loads"][li]["model"] == 8
+                     else spec["loads"][li].get("vlowpu", 0.5)) for li in f.elem_load])
+    keep = ~((np.abs(v / thr - 1.0) < 1e-9).any(1) | r["near_tol"])
+    assert keep.sum() >= 0.99 * K
+    print("%s: %d envs left out, %d stopped at the cap, iterations %s"
+          % (semantics, K - keep.sum(), (~r["converged"]).sum(), np.unique(r["it"])))
+    np.testing.assert_array_equal(np.abs(git)[keep], r["it"][keep])
+    np.testing.assert_array_equal((git > 0)[keep], r["converged"][keep])
+    np.testing.assert_allclose(g[keep], r["pu"][keep], rtol=1e-9, atol=0)
+
+
 def test_three_winding_and_centre_tap_transformers_vs_oracle():
     """3-winding and centre-tapped transformers (tests/data/xfmr3_feeder.dss,
     the native N-winding element): the fast kernel, the general kernel and
