@@ -771,6 +771,29 @@ int32_t pgw_reg_factor(const pgw_reg_params* p, int64_t n, const double* taps, c
  * where any tap moved (else 0); *n_changed (device int32) += that count. */
 int32_t pgw_reg_control(const pgw_reg_params* p, int64_t n, const double* reg_x, const double* reg_c,
                         double* taps, int32_t* active, int32_t* n_changed, void* stream);
+/* The snap solve with controls in one launch (OpenDSS SolveSnap: solve, sample
+ * the controls, execute the nearest actions, repeat until no control acts or
+ * max_passes solves): per block of 64 envs, pgw_pf_solve_general's solve for
+ * the envs still active, pgw_reg_control's pass on their x and c, and
+ * pgw_reg_factor for those whose taps moved, which are the next pass's active
+ * envs -- the same per-env arithmetic as the three entries called in a host
+ * loop over env_active, with no host synchronisation.  A re-solve starts from
+ * the direct solution at the new taps (PGW_PF_OPENDSS) or from the env's
+ * element voltages of the previous pass (PGW_PF_EXACT; the first pass from
+ * U_init where given).  Control and factor follow every solve, the last
+ * allowed one too.
+ * taps (n_ctrl x n) and Kreg (the buffer t->Kreg names) are read and written;
+ * passes (n, nullable): the solves each env got.  iters, v_out, v_min_out /
+ * v_max_out, U_out, reg_x and reg_c hold each env's last solve.  Needs
+ * p->n_reg > 0, reg->r_reg == p->r_reg, 1 <= max_passes <= 64, t->env_active
+ * == NULL; PGW_PF_OPENDSS_STEP is refused, and so is PGW_PF_OPENDSS with
+ * U_init (as pgw_pf_solve_general refuses it with RegControls: every re-solve
+ * under that rule starts from the direct solution). */
+int32_t pgw_pf_solve_regulated(const pgw_pfg_params* p, const pgw_pfg_tables* t,
+                               const pgw_reg_params* reg, int64_t n,
+                               const double* ctrl_p, const double* ctrl_q,
+                               double* taps, double* Kreg, int32_t max_passes,
+                               double* v_out, int32_t* iters, int32_t* passes, void* stream);
 
 /* ------------------------------------------------------------------------
  * Kernel timing (benchmark instrumentation): while on, every `every`-th launch

@@ -359,6 +359,8 @@ _SIGS = {
     "pgw_pf_solve_general": (i32, [P(PFGParams), P(PFGTables), i64, vp, vp, vp, vp, vp]),
     "pgw_reg_factor": (i32, [P(RegParams), i64, vp, vp, vp, vp]),
     "pgw_reg_control": (i32, [P(RegParams), i64, vp, vp, vp, vp, vp, vp]),
+    "pgw_pf_solve_regulated": (i32, [P(PFGParams), P(PFGTables), P(RegParams), i64, vp, vp, vp, vp, i32, vp, vp,
+                                     vp, vp]),
     "pgw_pf_padded_m": (i32, [i32]),
     "pgw_voltage_band_penalty": (i32, [i64, vp, f64, f64, f64, vp, vp]),
     "pgw_pf_pack_size": (i64, [i32]),

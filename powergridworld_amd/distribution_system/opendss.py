@@ -109,7 +109,8 @@ class OpenDSSSolver(PowerFlowSolver):
                  num_envs: int = 1, device=None, tol: float = None, max_iter: int = None,
                  output_nodes=None, predictor: bool = True, warm_start: bool = False,
                  convergence: str = "opendss", general: bool = None, od_table: bool = True,
-                 snap_start: str = "direct", yprim: str = "dss_file", **kwargs):
+                 snap_start: str = "direct", yprim: str = "dss_file", control_loop: str = "host",
+                 **kwargs):
         """convergence: "opendss" (the default) -- OpenDSS's own snap solve as
         the reference runs it (opendss.py:134):
         loads' nominal admittances in Y, start from the direct solution, stop at
@@ -136,8 +137,20 @@ class OpenDSSSolver(PowerFlowSolver):
         loads' Yeq (the hour's base loads and each env's controllable power):
         the general kernel with the hour's reduction and the controllable
         elements' per-env Yeq change as correction columns
-        (PGW_PF_OPENDSS_STEP); no response table, the generic multi-agent path."""
+        (PGW_PF_OPENDSS_STEP); no response table, the generic multi-agent path.
+        control_loop (feeders with RegControls; nothing changes without them):
+        "host" (the default) -- the snap solve with controls as a host loop of
+        pgw_pf_solve_general / pgw_reg_control / pgw_reg_factor launches, one
+        host synchronisation per control pass; "device" -- the whole loop in
+        one launch (pgw_pf_solve_regulated: each block of 64 envs runs its own
+        passes), no synchronisation, the same per-env arithmetic and results
+        bit for bit; control_passes then holds each env's solves, and the
+        fused multi-agent step (pgw_ma_step) serves the feeder.  Not with
+        snap_start="previous" on such a feeder (ValueError)."""
         super().__init__(**kwargs)
+        if control_loop not in ("host", "device"):
+            raise ValueError("control_loop must be 'host' or 'device', got %r" % (control_loop,))
+        self.control_loop = control_loop
         if convergence not in ("exact", "opendss"):
             raise ValueError("convergence must be 'exact' or 'opendss', got %r" % (convergence,))
         if snap_start not in ("direct", "previous"):
@@ -196,6 +209,11 @@ class OpenDSSSolver(PowerFlowSolver):
         self.regulators = self.feeder.regulators(Z=self._fd_iter.Z)
         if self.regulators is not None and yprim == "step":
             raise ValueError("yprim='step' with RegControls is not supported")
+        if self.regulators is not None and control_loop == "device" and snap_start == "previous":
+            # the kernel re-arms the direct-solution pass after every tap move, and
+            # both entries refuse the OpenDSS rule with U_init and RegControls
+            raise ValueError("control_loop='device' with snap_start='previous' and RegControls is not "
+                             "supported: a re-solve after a tap move starts from the direct solution")
         if self.regulators is not None:
             self._init_regulators()
         self._h1, self._h1_cache = None, {}
@@ -1371,7 +1389,28 @@ class OpenDSSSolver(PowerFlowSolver):
         self._reg_S = torch.tensor(np.ascontiguousarray(reg["S"]).view(np.float64).ravel(), device=dev)
         self._reg_rho = torch.tensor(reg["rho"], dtype=torch.float64, device=dev)
         self._reg_params = _lib.reg_params(reg, self._reg_S.data_ptr(), self._reg_rho.data_ptr())
+        # control_loop="device": the solves each env got in the last power flow
+        # ([N] int32, written by the kernel: an output like iterations).  A
+        # checkpoint saves and restores it like every tensor of the solver, in
+        # place and together with _control_iterations (None = "ask the
+        # device"), so control_iterations describes the restored step.
+        self.control_passes = (torch.zeros(n, dtype=torch.int32, device=dev)
+                               if self.control_loop == "device" else None)
         self.control_iterations = 0
+
+    @property
+    def control_iterations(self):
+        """Control passes of the last power flow (the most any env took).  With
+        control_loop="device" it is read from the device on request only
+        (control_passes.max(): a synchronisation)."""
+        it = self.__dict__.get("_control_iterations", 0)
+        if it is None:
+            it = self._control_iterations = int(self.control_passes.max())
+        return it
+
+    @control_iterations.setter
+    def control_iterations(self, v):
+        self._control_iterations = v
 
     def set_regulator_taps(self, taps):
         """Set every env's RegControl taps ([n_ctrl] or [n_ctrl, N], pu) and
@@ -1381,17 +1420,20 @@ class OpenDSSSolver(PowerFlowSolver):
         _lib.check(_lib.lib().pgw_reg_factor(self._reg_params, self.num_envs, self.reg_taps.data_ptr(), None,
                                              self._Kreg.data_ptr(), _lib.stream_ptr(self.device)))
 
-    def _solve_regulated(self, fn, p, tables, cp, cq):
-        """The control loop.  Exact mode: a re-solve after a tap move starts from
+    def _solve_regulated(self, fn, p, tables, cp, cq, v_out=None, iters=None):
+        """The control loop (v_out / iters: the solver's own buffers unless given).  Exact mode: a re-solve after a tap move starts from
         the env's solution of the previous pass (U_init = U_out of the same
         per-env buffer) -- the fixed point to tol in a few iterations instead of
         ~11 from the direct solution; the result depends only on this call's
         inputs and the taps it started from.  (OpenDSS mode keeps its
         direct-solution start)"""
         n, st, lib = self.num_envs, _lib.stream_ptr(self.device), _lib.lib()
+        v_out = self.v_out if v_out is None else v_out
+        iters = self._iters if iters is None else iters
         t = type(tables).from_buffer_copy(tables)
         t.Kreg, t.reg_x, t.reg_c = self._Kreg.data_ptr(), self._reg_x.data_ptr(), self._reg_c.data_ptr()
         t.reg_rho = self._reg_rho.data_ptr()
+        t.env_active = None
         warm = self.convergence == "exact"
         if warm:
             if getattr(self, "_reg_U", None) is None or self._reg_U.shape[1] != self.M:
@@ -1403,13 +1445,20 @@ class OpenDSSSolver(PowerFlowSolver):
                 # solution, as OpenDSS's snap solve does (history-dependent last bits)
                 t.U_init = self._reg_U.data_ptr()
             self._reg_U_valid = True
+        if self.control_loop == "device":
+            # the same loop per block of 64 envs in one launch, no host sync
+            _lib.check(lib.pgw_pf_solve_regulated(p, t, self._reg_params, n, _lib.dptr(cp), _lib.dptr(cq),
+                                                  self.reg_taps.data_ptr(), self._Kreg.data_ptr(),
+                                                  int(self.OPENDSS_MAX_CONTROL_ITER), _lib.dptr(v_out),
+                                                  _lib.dptr(iters), self.control_passes.data_ptr(), st))
+            self.control_iterations = None        # (control_passes.max() when asked for)
+            return
         active = None
         for it in range(1, self.OPENDSS_MAX_CONTROL_ITER + 1):
             if warm and it == 2:
                 t.U_init = self._reg_U.data_ptr()
             t.env_active = active
-            _lib.check(fn(p, t, n, _lib.dptr(cp), _lib.dptr(cq), _lib.dptr(self.v_out),
-                          _lib.dptr(self._iters), st))
+            _lib.check(fn(p, t, n, _lib.dptr(cp), _lib.dptr(cq), _lib.dptr(v_out), _lib.dptr(iters), st))
             self._reg_nchg.zero_()
             _lib.check(lib.pgw_reg_control(self._reg_params, n, self._reg_x.data_ptr(), self._reg_c.data_ptr(),
                                            self.reg_taps.data_ptr(), self._reg_active.data_ptr(),

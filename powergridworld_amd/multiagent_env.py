@@ -684,7 +684,12 @@ class MultiAgentEnv(Env):
         if not isinstance(self.pf_solver, OpenDSSSolver):
             return "power flow solver is not the batched OpenDSSSolver"
         if getattr(self.pf_solver, "regulators", None) is not None:
-            return "RegControl (the control loop runs in OpenDSSSolver.calculate_power_flow)"
+            # control_loop="device": the snap solve with controls is one launch
+            # (pgw_pf_solve_regulated) on the step's bus loads, fp64 only
+            if getattr(self.pf_solver, "control_loop", "host") != "device":
+                return "RegControl (the control loop runs in OpenDSSSolver.calculate_power_flow)"
+            if self.dtype != torch.float64:
+                return "RegControl on the fused multi-agent step is fp64 only"
         if getattr(self.pf_solver, "snap_start", "direct") != "direct":
             return "snap_start='previous' (each env's solve starts from its own previous solution)"
         if getattr(self.pf_solver, "yprim", "dss_file") != "dss_file":
@@ -802,7 +807,10 @@ class MultiAgentEnv(Env):
                     "iters": torch.zeros(n, dtype=torch.int32, device=dev),
                     "lazy_v": _FusedVoltages(self, {}, 0), "bufv": self._ma_bufv(plan),
                     "gen": ComponentEnv._bufv_gen, "fn": _lib.lib().pgw_ma_step_f32 if f32 else _lib.lib().pgw_ma_step,
-                    "general": _lib.lib().pgw_pf_solve_general if solver.general else None}
+                    "general": _lib.lib().pgw_pf_solve_general if solver.general else None,
+                    # RegControls (control_loop="device"): the solver's own launch of
+                    # pgw_pf_solve_regulated in place of the general power flow
+                    "regloop": solver.regulators is not None}
 
     @staticmethod
     def _ma_bufv(plan):
@@ -833,7 +841,18 @@ class MultiAgentEnv(Env):
             s_ = H["t"] % H["cap"]
             v_out = H["v"][s_].data_ptr()
         st = _lib.stream_ptr(self.device)
-        if M["general"] is None:
+        if M["regloop"]:
+            # the agents' step, then the snap solve with controls on its bus loads;
+            # every node into the history slot or the solver's own buffer (the taps
+            # move on, so no second solver can restate the step's other nodes)
+            rc = M["fn"](args, None, None, self.num_envs, None, None, st)
+            if rc:
+                _lib.check(rc)
+            if H is None:
+                solver.bind_output(None)
+            solver._solve_regulated(None, pfp, pft, M["bus_p"] if args.n_bus else None, None,
+                                    v_out=H["v"][s_] if H is not None else solver.v_out, iters=M["iters"])
+        elif M["general"] is None:
             rc = M["fn"](args, pfp, pft, self.num_envs, v_out, M["iters"].data_ptr(), st)
         else:     # the agents' step, then the general power flow on its bus loads
             rc = M["fn"](args, None, None, self.num_envs, None, None, st) or \
@@ -863,7 +882,10 @@ class MultiAgentEnv(Env):
             agent_power_p.append(agent.real_power)
         solver.iterations = M["iters"]
         self._fused_steps += 1
-        if H is None:
+        if H is None and M["regloop"]:
+            solver._prepare_bus_voltages()
+            self.voltages = solver.bus_voltages
+        elif H is None:
             # the extrema the epilogue wrote; every node solved on first access
             lazy = M["lazy_v"]
             lazy._step, lazy._reset, lazy._full = self._fused_steps, False, None
@@ -1132,7 +1154,8 @@ class MultiAgentEnv(Env):
         if not hasattr(solver, "_prepare_bus_voltages"):
             return
         H = self._hist
-        if H is not None or (self._fused is None and self._ma is None):
+        if H is not None or (self._fused is None and self._ma is None) or \
+                (self._ma is not None and self._ma["regloop"]):
             solver._prepare_bus_voltages()
             self.voltages = solver.bus_voltages
             return

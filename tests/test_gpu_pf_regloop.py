@@ -1,0 +1,373 @@
+"""The RegControl loop on the device (pgw_pf_solve_regulated, k_pf_regulated in
+csrc/pgw_pf_general.hip; OpenDSSSolver(control_loop="device")): one launch per
+snap solve with controls, each block of 64 envs running its own passes.  Needs
+an MI355X.
+
+Two independent references: the host loop of pgw_pf_solve_general /
+pgw_reg_control / pgw_reg_factor launches (bit for bit: both run the same
+device functions per env) and the oracle's per-env restatement of SolveSnap
+(oracle/pf_oracle.py Feeder.solve_regulated, with per-env pass counts and a
+pass cap).  Inputs are those of test_gpu_pf_general._regcontrol_vs_oracle:
+default_rng(11), starting taps taps0 + 0.00625 integers(-6, 7), two consecutive
+times with the taps carried.  Parity unpinned (no OpenDSS).
+"""
+import functools
+import os
+
+import numpy as np
+import pandas as pd
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+HERE = os.path.dirname(os.path.abspath(__file__))
+FEEDERS = {nm: os.path.join(HERE, "data", nm + "_feeder.dss") for nm in ("regctl", "regctl2", "regctl_w1")}
+SHAPE = "ieee_13_dss/annual_hourly_load_profile.csv"
+TIMES = [pd.Timestamp("08-12-2021 %02d:10:00" % h) for h in (3, 11, 17, 20)]
+K_ORACLE = 65
+
+
+def _solver(feeder, **kw):
+    from powergridworld_amd.distribution_system.opendss import OpenDSSSolver
+    return OpenDSSSolver(FEEDERS[feeder], SHAPE, device=DEV, **kw)
+
+
+@functools.lru_cache(maxsize=None)
+def _oracle(feeder):
+    from oracle.pf_oracle import BatchedPF
+    from powergridworld_amd.distribution_system.feeder import load_feeder_spec
+    return BatchedPF(spec=load_feeder_spec(FEEDERS[feeder]), system_load_rescale_factor=1.0)
+
+
+def _inputs(taps0, K):
+    """(starting taps [K, n_ctrl], [(time, p, q)] of the two steps)."""
+    rng = np.random.default_rng(11)
+    taps = taps0[None, :] + 0.00625 * rng.integers(-6, 7, size=(K, len(taps0)))
+    steps = []
+    for t in TIMES[1:3]:
+        p = rng.uniform(-300.0, 900.0, K)
+        steps.append((t, p, rng.uniform(-0.3, 0.5, K) * np.abs(p)))
+    return taps, steps
+
+
+def _snapshot(s):
+    """The buffers a regulated power flow leaves, cloned."""
+    torch.cuda.synchronize()
+    out = {"taps": s.reg_taps, "v": s.v_out, "iterations": s.iterations, "vmin": s._vmin, "vmax": s._vmax,
+           "Kreg": s._Kreg, "reg_x": s._reg_x, "reg_c": s._reg_c}
+    return {k: v.clone() for k, v in out.items()}
+
+
+def _run(feeder, semantics, K, loop, cap=None):
+    """Both steps on one solver: [snapshot per step], the solver."""
+    s = _solver(feeder, num_envs=K, convergence=semantics, control_loop=loop)
+    assert s.general and s.regulators is not None and s.control_loop == loop
+    if cap is not None:
+        s.OPENDSS_MAX_CONTROL_ITER = cap
+    taps, steps = _inputs(s.regulators["taps0"], K)
+    s.set_regulator_taps(torch.tensor(taps.T.copy(), device=DEV))
+    snaps = []
+    for t, p, q in steps:
+        s.calculate_power_flow({"f1": torch.tensor(p, device=DEV)}, {"f1": torch.tensor(q, device=DEV)},
+                               current_time=t)
+        snap = _snapshot(s)
+        if loop == "device":
+            snap["passes"] = s.control_passes.clone()
+        snap["control_iterations"] = s.control_iterations
+        snaps.append(snap)
+    return snaps, s
+
+
+@functools.lru_cache(maxsize=None)
+def _oracle_run(feeder, semantics, cap):
+    """The oracle's two steps at K_ORACLE envs: [(pu voltages, iterations, taps,
+    passes)] (computed once per case, shared, never modified)."""
+    o = _oracle(feeder)
+    f = o.feeder
+    from powergridworld_amd.distribution_system.feeder import Feeder
+    taps, steps = _inputs(Feeder(f.spec).regulators()["taps0"], K_ORACLE)
+    out = []
+    for t, p, q in steps:
+        kw, kvar = o.loads(t, {"f1": p}, {"f1": q}, K=K_ORACLE)
+        if semantics == "opendss":
+            V, it, tp, cp = f.solve_regulated(kw, kvar, taps, "opendss", f.base_kw, f.base_kvar,
+                                              max_control_iter=cap)
+        else:
+            V, it, tp, cp = f.solve_regulated(kw, kvar, taps, max_control_iter=cap)
+        for a in (V, it, tp, cp):
+            a.setflags(write=False)
+        out.append((f.pu(V), it, tp, cp))
+        taps = tp
+    return out
+
+
+def _assert_bit_equal(host, device):
+    for a, b in zip(host, device):
+        for key in ("taps", "v", "iterations", "vmin", "vmax", "Kreg", "reg_x", "reg_c"):
+            assert torch.equal(a[key], b[key]), key
+        assert b["control_iterations"] == int(b["passes"].max())
+        assert a["control_iterations"] == b["control_iterations"]
+
+
+@pytest.mark.parametrize("n", [1, 65, 192])
+@pytest.mark.parametrize("feeder", ["regctl", "regctl2", "regctl_w1"])
+@pytest.mark.parametrize("semantics", ["exact", "opendss"])
+def test_device_loop_equals_host_loop(semantics, feeder, n):
+    """The device loop against the host loop on the same inputs, bit for bit:
+    taps, every node voltage, iterations, extrema, K, x and c; n = 1 is a
+    one-env block, n = 65 has a last block holding one env."""
+    host, _ = _run(feeder, semantics, n, "host")
+    device, s = _run(feeder, semantics, n, "device")
+    _assert_bit_equal(host, device)
+    assert s.control_passes.dtype == torch.int32 and tuple(s.control_passes.shape) == (n,)
+    assert int(s.control_passes.min()) >= 1
+
+
+@pytest.mark.parametrize("feeder", ["regctl", "regctl2", "regctl_w1"])
+@pytest.mark.parametrize("semantics", ["exact", "opendss"])
+def test_device_loop_vs_oracle(semantics, feeder):
+    """The device loop against the oracle's SolveSnap restatement: the same
+    taps exactly, voltages within 1e-9 rel (test_regcontrol_vs_oracle's
+    tolerance), the OpenDSS rule's iteration counts, and each env's pass count.
+    The batch exercises the loop: over the two steps the oracle's counts hold
+    an env with one pass, one with three or more and three distinct values."""
+    ref = _oracle_run(feeder, semantics, 15)
+    counts = np.concatenate([cp for _, _, _, cp in ref])
+    assert counts.min() == 1 and counts.max() >= 3 and len(np.unique(counts)) >= 3
+    device, s = _run(feeder, semantics, K_ORACLE, "device")
+    names = _oracle(feeder).feeder.node_names
+    rows = [s.output_names.index(nm) for nm in names]
+    for snap, (pu, it, tp, cp) in zip(device, ref):
+        np.testing.assert_array_equal(snap["taps"].cpu().numpy().T, tp)
+        np.testing.assert_allclose(snap["v"].cpu().numpy()[rows].T, pu, rtol=1e-9, atol=0)
+        if semantics == "opendss":
+            np.testing.assert_array_equal(snap["iterations"].cpu().numpy(), it)
+        np.testing.assert_array_equal(snap["passes"].cpu().numpy(), cp)
+
+
+@pytest.mark.parametrize("feeder", ["regctl", "regctl2"])
+@pytest.mark.parametrize("semantics", ["exact", "opendss"])
+def test_pass_cap(semantics, feeder):
+    """MaxControlIterations = 2: control and factor follow the last allowed
+    solve too, so the taps are those after the second control pass -- the
+    oracle's with max_control_iter=2, which cuts envs short of their uncapped
+    taps -- no env gets more than two solves, and host and device agree bit for
+    bit."""
+    ref, free = _oracle_run(feeder, semantics, 2), _oracle_run(feeder, semantics, 15)
+    assert (ref[0][3] == 2).sum() > 0 and (ref[0][2] != free[0][2]).any()     # the cap binds
+    host, _ = _run(feeder, semantics, K_ORACLE, "host", cap=2)
+    device, _ = _run(feeder, semantics, K_ORACLE, "device", cap=2)
+    _assert_bit_equal(host, device)
+    for snap, (pu, it, tp, cp) in zip(device, ref):
+        np.testing.assert_array_equal(snap["taps"].cpu().numpy().T, tp)
+        assert int(snap["passes"].max()) <= 2
+        np.testing.assert_array_equal(snap["passes"].cpu().numpy(), cp)
+
+
+def test_direct_abi_argument_checks():
+    """pgw_pf_solve_regulated refuses max_passes = 0, env_active != NULL, n_reg =
+    0, a reg->r_reg that does not match and PGW_PF_OPENDSS_STEP with a non-zero
+    status and no launch (the buffers stay as they were); n = 0 is PGW_OK; the
+    valid call then moves taps."""
+    from powergridworld_amd import _lib
+    n = 64
+    s = _solver("regctl", num_envs=n, convergence="opendss", control_loop="device")
+    s.set_controllable_loads(["f1"])
+    taps, steps = _inputs(s.regulators["taps0"], n)
+    s.set_regulator_taps(torch.tensor(taps.T.copy(), device=DEV))
+    lib, st = _lib.lib(), _lib.stream_ptr(s.device)
+    p = s.step_params(steps[0][0])
+    t = _lib.PFGTables.from_buffer_copy(s.solve_tables(steps[0][0], True))
+    cp = torch.tensor(steps[0][1], device=DEV).reshape(1, n)
+    passes = torch.full((n,), -7, dtype=torch.int32, device=DEV)
+    before = {k: v.clone() for k, v in (("taps", s.reg_taps), ("K", s._Kreg), ("v", s.v_out))}
+
+    def call(p_=p, t_=t, reg=s._reg_params, n_=n, max_passes=15):
+        return lib.pgw_pf_solve_regulated(p_, t_, reg, n_, cp.data_ptr(), None, s.reg_taps.data_ptr(),
+                                          s._Kreg.data_ptr(), max_passes, s.v_out.data_ptr(),
+                                          s._iters.data_ptr(), passes.data_ptr(), st)
+
+    def edited(obj, **kw):
+        c = type(obj).from_buffer_copy(obj)
+        for k, v in kw.items():
+            setattr(c, k, v)
+        return c
+
+    active = torch.ones(n, dtype=torch.int32, device=DEV)
+    bad = {"max_passes = 0": dict(max_passes=0),
+           "max_passes = 65": dict(max_passes=65),
+           "env_active": dict(t_=edited(t, env_active=active.data_ptr())),
+           "n_reg = 0": dict(p_=edited(p, n_reg=0, r_reg=0)),
+           "r_reg mismatch": dict(reg=edited(s._reg_params, r_reg=s._reg_params.r_reg - 1)),
+           "OPENDSS_STEP": dict(p_=edited(p, mode=_lib.PF_OPENDSS_STEP)),
+           # the OpenDSS rule with a start per env (snap_start="previous"): refused, as
+           # pgw_pf_solve_general refuses it with RegControls
+           "OPENDSS with U_init": dict(t_=edited(t, U_init=torch.zeros((n, s.M, 2), dtype=torch.float64,
+                                                                       device=DEV).data_ptr()))}
+    for what, kw in bad.items():
+        assert call(**kw) != 0, what
+        msg = lib.pgw_last_error().decode()
+        assert msg.startswith("pgw_pf_solve_regulated: "), (what, msg)     # the entry that was called
+    assert call(n_=0) == 0
+    torch.cuda.synchronize()
+    assert int((passes != -7).sum()) == 0
+    assert torch.equal(before["taps"], s.reg_taps) and torch.equal(before["K"], s._Kreg)
+    assert torch.equal(before["v"], s.v_out)
+    assert call() == 0
+    torch.cuda.synchronize()
+    assert int(passes.min()) >= 1 and int(passes.max()) >= 3
+    assert not torch.equal(before["taps"], s.reg_taps)
+
+
+def test_device_loop_refuses_snap_start_previous():
+    """snap_start="previous" (each env's snap solve continues from its previous
+    solution) cannot hold on the device loop, whose re-solves start from the
+    direct solution: refused at construction, not at the second power flow.
+    Without RegControls control_loop="device" changes nothing and is accepted."""
+    with pytest.raises(ValueError, match="snap_start"):
+        _solver("regctl", num_envs=8, convergence="opendss", snap_start="previous", control_loop="device")
+    from powergridworld_amd.distribution_system.opendss import OpenDSSSolver
+    s = OpenDSSSolver("ieee_13_dss/IEEE13Nodeckt.dss", SHAPE, device=DEV, num_envs=8, snap_start="previous",
+                      control_loop="device")
+    assert s.regulators is None and s.control_loop == "device"
+
+
+def T(x):
+    return torch.tensor(np.asarray(x, dtype=np.float64), device=DEV)
+
+
+def _ma_env(K, control_loop=None, **kw):
+    """test_regcontrol_multiagent_generic_path's configuration."""
+    from powergridworld_amd.agents import EnergyStorageEnv
+    from powergridworld_amd.agents.vehicles import EVChargingEnv
+    from powergridworld_amd.distribution_system.opendss import OpenDSSSolver
+    from powergridworld_amd.multiagent_env import MultiAgentEnv
+    from powergridworld_amd.scenarios.heterogeneous import ThisPVEnv
+    pf = {"feeder_file": FEEDERS["regctl"], "loadshape_file": SHAPE, "system_load_rescale_factor": 1.0,
+          "convergence": "exact"}
+    if control_loop is not None:
+        pf["control_loop"] = control_loop
+    cfg = {"common_config": {"start_time": "08-12-2020 06:00:00", "end_time": "08-13-2020 00:00:00",
+                             "control_timedelta": pd.Timedelta(300, "s")},
+           "pf_config": {"cls": OpenDSSSolver, "config": pf},
+           "agents": [
+               {"name": "pv", "bus": "f1", "cls": ThisPVEnv,
+                "config": {"profile_csv": "off-peak.csv", "scaling_factor": 400., "grid_aware": True}},
+               {"name": "ev", "bus": "a1", "cls": EVChargingEnv,
+                "config": {"num_vehicles": 25, "minutes_per_step": 5, "max_charge_rate_kw": 7.,
+                           "peak_threshold": 200., "vehicle_multiplier": 20.}},
+               {"name": "storage", "bus": "f2", "cls": EnergyStorageEnv,
+                "config": {"max_power": 150., "storage_range": (3., 250.)}}]}
+    env = MultiAgentEnv(**cfg, num_envs=K, device=DEV, **kw)
+    for k, a in enumerate(env.agents):         # the sampled initial states, the same in every env built here
+        if hasattr(a, "seed"):
+            a.seed(50 + k)
+    return env
+
+
+def _actions(rng, K):
+    return {"pv": T(rng.uniform(-1, 1, (K, 1))), "ev": T(rng.uniform(-1, 1, (K, 1))),
+            "storage": T(rng.uniform(-1, 1, (K, 1)))}
+
+
+def _node_voltages(env, names):
+    bv = env.pf_solver.get_bus_voltages()
+    return torch.stack([bv[nm] for nm in names])
+
+
+def _flat(x):
+    if isinstance(x, dict):
+        return [t for k in sorted(x) for t in _flat(x[k])]
+    return [x] if isinstance(x, torch.Tensor) else []
+
+
+@pytest.mark.parametrize("history,steps", [(False, 12), (True, 3)])
+def test_fused_step_on_regulated_feeder(history, steps):
+    """MultiAgentEnv on the RegControl feeder with control_loop="device": the
+    fused multi-agent step serves it (pgw_ma_step, then pgw_pf_solve_regulated
+    on its bus loads).  Taps exactly and voltages within 1e-9 of the oracle
+    driven by the agents' own real powers; every observation, reward, tap and
+    node voltage bit-equal to the generic path with the host loop on the same
+    actions; a tap moves.  record_history=True covers the v_out ring slot."""
+    K = 128
+    env = _ma_env(K, "device", record_history=history)
+    gen = _ma_env(K, record_history=history)
+    assert env._fused is None and env._ma is not None and env._ma["regloop"]
+    assert gen._fused is None and gen._ma is None and gen.pf_solver.control_loop == "host"
+    o = _oracle("regctl")
+    f = o.feeder
+    obs_e, obs_g = env.reset(), gen.reset()
+    for a, b in zip(_flat(obs_e), _flat(obs_g)):
+        assert torch.equal(a, b)
+    s = env.pf_solver
+    taps = s.reg_taps.cpu().numpy().T.copy()
+    start = taps.copy()
+    rng = np.random.default_rng(21)
+    for _ in range(steps):
+        a = _actions(rng, K)
+        oe, re_, _, _ = env.step(a)
+        og, rg, _, _ = gen.step({k: v.clone() for k, v in a.items()})
+        torch.cuda.synchronize()
+        fe, fg = _flat(oe) + _flat(re_), _flat(og) + _flat(rg)
+        assert len(fe) == len(fg) and len(fe) >= 6
+        for x, y in zip(fe, fg):
+            assert torch.equal(x, y)
+        assert torch.equal(s.reg_taps, gen.pf_solver.reg_taps)
+        assert torch.equal(_node_voltages(env, f.node_names), _node_voltages(gen, f.node_names))
+        assert torch.equal(s.iterations, gen.pf_solver.iterations)
+        p = {bus: env.agent_dict[nm].real_power.cpu().numpy() for nm, bus in (("pv", "f1"), ("ev", "a1"),
+                                                                              ("storage", "f2"))}
+        kw, kvar = o.loads(env.time, p, None, K=K)
+        V, it, tp, cp = f.solve_regulated(kw, kvar, taps)
+        np.testing.assert_array_equal(s.reg_taps.cpu().numpy().T, tp)
+        np.testing.assert_allclose(_node_voltages(env, f.node_names).cpu().numpy().T, f.pu(V), rtol=1e-9, atol=0)
+        np.testing.assert_array_equal(s.control_passes.cpu().numpy(), cp)
+        taps = tp
+    if not history:
+        assert (taps != start).any()
+    else:
+        ve, _, _ = env.voltage_history()
+        vg, _, _ = gen.voltage_history()
+        assert ve.shape[0] == steps and torch.equal(ve, vg)
+
+
+def test_fused_regulated_step_keeps_refusing_fp32_and_coordinated():
+    """fp32 storage with RegControls raises as before, and the host-loop default
+    keeps the fused paths aside."""
+    with pytest.raises(ValueError):
+        _ma_env(64, "device", dtype=torch.float32)
+    env = _ma_env(64)
+    assert env._ma is None and "RegControl" in env._ma_fusable()
+    assert "RegControl" in _ma_env(64, "device")._fusable()
+
+
+def test_checkpoint_mid_run():
+    """state_dict() mid-run on the device-loop env, three more steps,
+    load_state_dict(), the same three steps again: the same taps and voltages."""
+    K = 64
+    env = _ma_env(K, "device")
+    env.reset()
+    rng = np.random.default_rng(5)
+    names = env.pf_solver.feeder.node_names
+    for _ in range(4):
+        env.step(_actions(rng, K))
+    sd = env.state_dict()
+    acts = [_actions(rng, K) for _ in range(3)]
+
+    def three():
+        out = []
+        for a in acts:
+            env.step(a)
+            torch.cuda.synchronize()
+            out.append((env.pf_solver.reg_taps.clone(), _node_voltages(env, names).clone(),
+                        env.pf_solver.control_passes.clone()))
+        return out
+
+    first = three()
+    env.load_state_dict(sd)
+    second = three()
+    assert any(not torch.equal(first[0][0], x[0]) for x in first[1:]) or int(first[0][2].max()) > 1
+    for a, b in zip(first, second):
+        for x, y in zip(a, b):
+            assert torch.equal(x, y)
