@@ -354,7 +354,7 @@ class Ref:
         L = ((np.abs(c) + v * (np.abs(sr) * dp + np.abs(si) * dq)) * (1 + 1e-6)).astype(float)
         return J, A, L, br
 
-    def one_pass(self, u, sr, si, e_in=None, K=None, zero_J=False):
+    def one_pass(self, u, sr, si, e_in=None, K=None, zero_J=False, dK=None):
         """One pass from voltages u [n, m] whose components are known to e_in
         [n, m] (0: exact inputs).  Returns a dict: u (new), Vc (check rows,
         complex), J, A, x, c, br, and the componentwise bounds e_u, e_vc and the
@@ -368,7 +368,9 @@ class Ref:
         (2 r + 2) 2^-53 sum |K_jl| rho_l |x_l| + sum |K_jl| rho_l sqrt2 ex_l,
         and every row gains the c columns: their amplitude sum |M_i,m+j|
         sum_l |K_jl| rho_l |x_l| inside the FMA term and sum |M_i,m+j| sqrt2
-        ec_j outside it."""
+        ec_j outside it.  dK [n] (tests/_regloop_direct_common.py): K itself is
+        known to |dK_jl| <= dK per env, which adds dK sum_l rho_l |x_l| to every
+        row of ec."""
         p = self.p
         m, mt = p.m, p.mtot
         n = u.shape[0]
@@ -391,6 +393,8 @@ class Ref:
             Ac[:, :r] = np.einsum("ejl,el->ej", aK, np.abs(x[:, :r]).astype(float))
             ec = np.zeros((n, p.n_reg))
             ec[:, :r] = (2 * r + 2) * U53 * Ac[:, :r] + np.einsum("ejl,el->ej", aK, SQRT2 * ex[:, :r])
+            if dK is not None:
+                ec[:, :r] += (np.asarray(dK, float)[:n] * (p.rho * np.abs(x[:, :r]).astype(float)).sum(1))[:, None]
             cols = np.concatenate([J, c], 1)
             amp = np.concatenate([A, Ac], 1)
             dcol = np.concatenate([dJ, SQRT2 * ec], 1)
@@ -419,11 +423,13 @@ class Ref:
         t2 = np.where(p.model == 8, p.vcut2, p.vlo2)
         return (np.abs(v2 / t2 - 1.0) < 2 * KNIFE).any(1)
 
-    def solve(self, n, ctrl_p, ctrl_q, tol, min_iter, max_iter, U_init=None, K=None):
+    def solve(self, n, ctrl_p, ctrl_q, tol, min_iter, max_iter, U_init=None, K=None, e_init=None, dK=None):
         """The header's iteration, every env on its own (a stopped env keeps
         its state): returns a dict with u, e_u, V, e_v (output rows), iters
         (signed as pgw.h: -count where stopped at max_iter unconverged), x, c,
-        e_x, e_c, excluded [n] (knife edges) and passes (the passes' dicts)."""
+        e_x, e_c, excluded [n] (knife edges) and passes (the passes' dicts).
+        e_init [n, m]: the bound U_init is known to (None: exact inputs);
+        dK: see one_pass."""
         p = self.p
         od = self.mode == PF_OPENDSS
         sr, si = self.powers(n, ctrl_p, ctrl_q)
@@ -432,8 +438,10 @@ class Ref:
         old = np.tile(np.abs(self.V0c), (n, 1)) if od else None
         if U_init is not None:
             u = U_init[:n].astype(CLD)
+            if e_init is not None:
+                e_u = np.array(e_init[:n], float)
         elif p.n_reg:                                   # the direct solution at the env's taps
-            ps = self.one_pass(np.tile(self.U0, (n, 1)), sr, si, None, K, zero_J=True)
+            ps = self.one_pass(np.tile(self.U0, (n, 1)), sr, si, None, K, zero_J=True, dK=dK)
             u, e_u = ps["u"], ps["e_u"]
             if od:
                 old = np.abs(ps["Vc"])
@@ -444,7 +452,7 @@ class Ref:
         conv_ok = np.zeros(n, bool)
         last = None
         for it in range(1, max_iter + 1):
-            ps = self.one_pass(u, sr, si, e_u, K)
+            ps = self.one_pass(u, sr, si, e_u, K, dK=dK)
             excluded |= active & self.knife(u)
             if od:
                 mag = np.abs(ps["Vc"])

@@ -727,6 +727,58 @@ def test_regcontrol_winding_1_model():
     assert tp[0][0] == 1.1
 
 
+REGCTL_WIDE = os.path.join(REPO, "tests", "data", "regctl_wide_feeder.dss")
+
+
+def test_regcontrol_wide_feeder_model():
+    """tests/data/regctl_wide_feeder.dss (regctl2's regulators on a wider
+    network): 36 nodes -- more than one chunk round of OpenDSS check rows --
+    with 21 load phase elements, so that the padded element rows and the 24
+    regulator columns stay within 64; the control records are regctl2's; the
+    Woodbury model gives the rebuilt network's voltages at every node, the new
+    buses' included; the oracle's loop at half load ends in band, at Vlimit or
+    at a tap limit.  Parity unpinned (no OpenDSS)."""
+    from oracle.pf_oracle import Feeder as OracleFeeder
+    from powergridworld_amd.distribution_system.feeder import Feeder, load_feeder_spec
+    spec = load_feeder_spec(REGCTL_WIDE)
+    f, o = Feeder(spec), OracleFeeder(spec)
+    reg, reg2 = f.regulators(), Feeder(load_feeder_spec(REGCTL2)).regulators()
+    R = reg["nodes"]
+    assert len(f.node_names) == 36 and 32 < len(o.node_names) <= 64
+    assert {"b9.1", "b10.2", "b11.3"} <= set(f.node_names)
+    m = sum(ld["phases"] for ld in spec["loads"] if int(ld.get("model", 1)) != 2)
+    assert m == 21 and -(-m // 8) * 8 + 24 <= 64
+    assert {"f1", "a1"} <= {ld["name"] for ld in spec["loads"]}
+    assert len(reg["phases"]) == 9 and len(R) == 21 and len(reg["ctrls"]) == 5
+    name = lambda rg, ff, j: ff.node_names[rg["nodes"][j]]
+    for c, c2 in zip(reg["ctrls"], reg2["ctrls"]):
+        for key in ("name", "n_mon", "pick", "winding", "max_tap_change", "ldc", "inverse_time", "vreg", "band",
+                    "ptratio", "ctprim", "r_ldc", "x_ldc", "vbase", "incr", "min_tap", "max_tap", "delay", "vlimit"):
+            assert c[key] == c2[key], (c["name"], key)
+    np.testing.assert_array_equal(reg["taps0"], reg2["taps0"])
+    r = len(R)
+    rng = np.random.default_rng(3)
+    for _ in range(3):
+        taps = reg["taps0"] + 0.00625 * rng.integers(-8, 9, size=len(reg["ctrls"]))
+        D = np.zeros((r, r), complex)
+        for ph in reg["phases"]:
+            t = taps[ph["ctrl"]]
+            t1 = t if ph["tap_winding"] == 1 else ph["tap1"]
+            t2 = t if ph["tap_winding"] == 2 else ph["tap2"]
+            Y = lambda a, b: np.array([[ph["A"] / a ** 2, ph["B"] / (a * b)], [ph["B"] / (a * b), ph["C"] / b ** 2]])
+            D[np.ix_([ph["a"], ph["b"]], [ph["a"], ph["b"]])] += Y(t1, t2) - Y(ph["tap1"], ph["tap2"])
+        K = np.linalg.solve(np.eye(r) + D @ reg["S"], D)
+        V = f.V0 - f.Z[:, R] @ (K @ f.V0[R])
+        ot = o.with_taps(list(taps))
+        np.testing.assert_allclose(V, ot.V0, rtol=1e-9, atol=1e-9 * np.abs(ot.V0).max())
+    kw = np.array([ld["kw"] for ld in spec["loads"]], float)
+    kvar = np.array([ld["kvar"] for ld in spec["loads"]], float)
+    V, it, tp, cp = o.solve_regulated(0.5 * kw[None], 0.5 * kvar[None], reg["taps0"][None])
+    assert 2 <= cp[0] < 15 and (tp[0] != reg["taps0"]).any()
+    _, moved = o.reg_control_pass(V[0], list(tp[0]))
+    assert not moved
+
+
 def test_regcontrol_options_oracle_semantics():
     """The oracle's Sample options on regctl2_feeder.dss, from chosen taps:
     Vlimit forces Reg2 down while its local voltage is above the limit

@@ -10,6 +10,12 @@ device functions per env) and the oracle's per-env restatement of SolveSnap
 pass cap).  Inputs are those of test_gpu_pf_general._regcontrol_vs_oracle:
 default_rng(11), starting taps taps0 + 0.00625 integers(-6, 7), two consecutive
 times with the taps carried.  Parity unpinned (no OpenDSS).
+
+regctl_wide_feeder.dss (36 nodes, 24 padded element rows + 24 regulator
+columns) is the feeder that takes k_pf_regulated beyond one check chunk per
+wave: <2, 2> under the OpenDSS rule, against the oracle's network re-inverted
+per tap tuple; tests/test_gpu_pf_regloop_direct.py runs every instantiation
+on synthetic problems.
 """
 import functools
 import os
@@ -22,7 +28,7 @@ import torch
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 HERE = os.path.dirname(os.path.abspath(__file__))
-FEEDERS = {nm: os.path.join(HERE, "data", nm + "_feeder.dss") for nm in ("regctl", "regctl2", "regctl_w1")}
+FEEDERS = {nm: os.path.join(HERE, "data", nm + "_feeder.dss") for nm in ("regctl", "regctl2", "regctl_w1", "regctl_wide")}
 SHAPE = "ieee_13_dss/annual_hourly_load_profile.csv"
 TIMES = [pd.Timestamp("08-12-2021 %02d:10:00" % h) for h in (3, 11, 17, 20)]
 K_ORACLE = 65
@@ -111,7 +117,7 @@ def _assert_bit_equal(host, device):
 
 
 @pytest.mark.parametrize("n", [1, 65, 192])
-@pytest.mark.parametrize("feeder", ["regctl", "regctl2", "regctl_w1"])
+@pytest.mark.parametrize("feeder", ["regctl", "regctl2", "regctl_w1", "regctl_wide"])
 @pytest.mark.parametrize("semantics", ["exact", "opendss"])
 def test_device_loop_equals_host_loop(semantics, feeder, n):
     """The device loop against the host loop on the same inputs, bit for bit:
@@ -124,7 +130,7 @@ def test_device_loop_equals_host_loop(semantics, feeder, n):
     assert int(s.control_passes.min()) >= 1
 
 
-@pytest.mark.parametrize("feeder", ["regctl", "regctl2", "regctl_w1"])
+@pytest.mark.parametrize("feeder", ["regctl", "regctl2", "regctl_w1", "regctl_wide"])
 @pytest.mark.parametrize("semantics", ["exact", "opendss"])
 def test_device_loop_vs_oracle(semantics, feeder):
     """The device loop against the oracle's SolveSnap restatement: the same
@@ -146,7 +152,7 @@ def test_device_loop_vs_oracle(semantics, feeder):
         np.testing.assert_array_equal(snap["passes"].cpu().numpy(), cp)
 
 
-@pytest.mark.parametrize("feeder", ["regctl", "regctl2"])
+@pytest.mark.parametrize("feeder", ["regctl", "regctl2", "regctl_wide"])
 @pytest.mark.parametrize("semantics", ["exact", "opendss"])
 def test_pass_cap(semantics, feeder):
     """MaxControlIterations = 2: control and factor follow the last allowed

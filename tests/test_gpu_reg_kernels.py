@@ -23,6 +23,8 @@ import numpy as np
 import pytest
 import torch
 
+from tests._regloop_direct_common import Model, _dev_S_rho, _ref_K, _synthetic_model, _tri    # noqa: F401
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -36,22 +38,8 @@ STEP = 0.00625                  # the feeders' tap step, (1.1 - 0.9) / 32
 
 
 # ---------------------------------------------------------------- the models
-class Model:
-    """What one pgw_reg_params describes, host side (phases: dicts of a, b,
-    ctrl, tap_winding, A, B, C, tap1, tap2; S: r x r complex; taps0: the
-    controls' DSS taps) and device side (rp, whose S / rho point into `keep`)."""
-
-    def __init__(self, r, phases, taps0, S, rp, keep, reg=None):
-        self.r, self.phases, self.taps0, self.S, self.rp, self.keep, self.reg = r, phases, taps0, S, rp, keep, reg
-        self.n_ctrl = len(taps0)
-        self.n_tri = r * (r + 1) // 2
-
-
-def _dev_S_rho(S, rho):
-    return (torch.tensor(np.ascontiguousarray(S).view(np.float64).ravel(), device=DEV),
-            torch.tensor(np.asarray(rho, float), dtype=torch.float64, device=DEV))
-
-
+# (Model, the synthetic models and the extended-precision factor live in
+# tests/_regloop_direct_common.py, shared with the control loop's tests)
 def _feeder_path(name):
     return os.path.join(HERE, "data", name + "_feeder.dss")
 
@@ -63,67 +51,6 @@ def _feeder_model(name):
     keep = _dev_S_rho(reg["S"], reg["rho"])
     rp = _lib.reg_params(reg, keep[0].data_ptr(), keep[1].data_ptr())
     return Model(len(reg["nodes"]), reg["phases"], reg["taps0"], reg["S"], rp, keep, reg)
-
-
-def _synthetic_model(r):
-    """r regulator nodes, min(r // 2, 12) regulated phases over random node
-    pairs a != b (nodes may be shared between phases), tap windings mixed 1
-    and 2, about three phases per control; A, B, C of the feeders' magnitude
-    (|y| 800 .. 2100 S at -45 degrees there) with a turns ratio near 1; S
-    exactly complex symmetric with a positive-definite real part, entries of
-    the feeders' S's magnitude (|S_jj| 0.9 .. 1.9 ohm there).
-
-    The scale of S matters to the bound the factor is held to.  pgw.h's D(t) =
-    Y(t) - Y(DSS taps) cancels: one tap step (0.00625) off the DSS tap,
-    |D| = |A| / 80, so rounding A / t^2 alone leaves D with a relative error of
-    ~100 x 2^-52 in any float64 evaluation of that formula.  K = (I + D S)^-1 D
-    damps it by |(I + S D)^-1| ~ 1 / (1 + |D S|): to a few 2^-52 where
-    |D S| >> 1, as on the feeders (|A| |S| / 80 ~ 10 .. 50 per step), and not
-    for a weakly coupled model -- with S halved the two-node model (kappa ~ 5)
-    needed 6 kappa 2^-52 in a float64 NumPy transcription of the kernel, with
-    this S 2.9.  Hence S of the feeders' size, not smaller."""
-    from powergridworld_amd import _lib
-    rng = np.random.default_rng(1000 + r)
-    nq = min(r // 2, _lib.REG_MAX_PHASES)
-    nc = max(1, nq // 3)
-    taps0 = 1.0 + STEP * rng.integers(-3, 4, size=nc)
-    phases = []
-    for q in range(nq):
-        a, b = (int(x) for x in rng.choice(r, 2, replace=False))
-        g = q % nc
-        tw = int(rng.integers(1, 3))
-        y = rng.uniform(800.0, 2100.0) * np.exp(-1j * np.deg2rad(rng.uniform(40.0, 80.0)))
-        nr = rng.uniform(0.9, 1.1)
-        other = 1.0 + STEP * int(rng.integers(-3, 4))
-        phases.append(dict(a=a, b=b, ctrl=g, tap_winding=tw, A=complex(y), B=complex(-y * nr),
-                           C=complex(y * nr * nr), tap1=float(taps0[g]) if tw == 1 else other,
-                           tap2=float(taps0[g]) if tw == 2 else other))
-    G = rng.normal(size=(r, r))
-    H = rng.normal(size=(r, r))
-    re = G @ G.T / r + 0.05 * np.eye(r)
-    re = 0.5 * (re + re.T)                       # x + y == y + x: exactly symmetric
-    im = 0.5 * (H + H.T)
-    S = re + 1j * im
-    assert (S == S.T).all() and np.linalg.eigvalsh(S.real).min() > 0.0
-    keep = _dev_S_rho(S, np.ones(r))
-    rp = _lib.RegParams()
-    rp.n_reg, rp.r_reg, rp.n_phase, rp.n_ctrl = -(-r // 8) * 8, r, nq, nc
-    for q, ph in enumerate(phases):
-        d = rp.phase[q]
-        d.a, d.b, d.ctrl, d.tap_winding = ph["a"], ph["b"], ph["ctrl"], ph["tap_winding"]
-        d.A[0], d.A[1] = ph["A"].real, ph["A"].imag
-        d.B[0], d.B[1] = ph["B"].real, ph["B"].imag
-        d.C[0], d.C[1] = ph["C"].real, ph["C"].imag
-        d.tap1, d.tap2 = ph["tap1"], ph["tap2"]
-    for g in range(nc):                           # control records that pass the argument check
-        d = rp.ctrl[g]
-        q0 = g                                    # (phase g follows control g)
-        d.n_mon, d.pick, d.winding, d.max_tap_change, d.vlim_node = 1, _lib.REG_PICK_PHASE, 2, 16, -1
-        d.mon_node[0], d.mon_phase[0] = phases[q0]["b"], q0
-        d.vreg, d.band, d.ptratio, d.ctprim, d.vbase = 120.0, 2.0, 20.0, 300.0, 120.0
-        d.incr, d.min_tap, d.max_tap, d.delay = STEP, 0.9, 1.1, 15.0
-    rp.S, rp.rho = keep[0].data_ptr(), keep[1].data_ptr()
-    return Model(r, phases, taps0, S, rp, keep)
 
 
 @functools.lru_cache(maxsize=None)
@@ -141,61 +68,6 @@ def _taps(name):
 
 
 # ------------------------------------------------------------- the reference
-def _tri(r):
-    """(i, l) of the packed upper triangle, in pgw_pfg_tables.Kreg's order."""
-    i, l = np.triu_indices(r)
-    assert all(int(i[k]) * r - int(i[k]) * (int(i[k]) - 1) // 2 + int(l[k]) - int(i[k]) == k for k in range(len(i)))
-    return i, l
-
-
-def _ref_K(m, taps):
-    """One env's K = (I + D S)^-1 D from pgw.h's formulas in 50-digit mpmath
-    arithmetic (every input taken at its float64 value): Gauss-Jordan with
-    partial pivoting on [I + D S | D].  Returns (K as complex128, what that
-    rounding left, kappa_2(I + D S)), or None where I + D S is singular."""
-    import mpmath as mp
-    with mp.workdps(50):
-        r = m.r
-        zero = mp.mpc(0)
-        D = [[zero] * r for _ in range(r)]
-        for ph in m.phases:
-            t = mp.mpf(float(taps[ph["ctrl"]]))
-            tap1, tap2 = mp.mpf(ph["tap1"]), mp.mpf(ph["tap2"])
-            t1 = t if ph["tap_winding"] == 1 else tap1
-            t2 = t if ph["tap_winding"] == 2 else tap2
-            A, B, C = mp.mpc(ph["A"]), mp.mpc(ph["B"]), mp.mpc(ph["C"])
-            a, b = ph["a"], ph["b"]
-            dab = B / (t1 * t2) - B / (tap1 * tap2)
-            D[a][a] += A / (t1 * t1) - A / (tap1 * tap1)
-            D[a][b] += dab
-            D[b][a] += dab
-            D[b][b] += C / (t2 * t2) - C / (tap2 * tap2)
-        S = [[mp.mpc(complex(x)) for x in row] for row in m.S]
-        M = []
-        for i in range(r):
-            nz = [(k, D[i][k]) for k in range(r) if D[i][k] != 0]
-            M.append([(1 if i == j else 0) + sum((d * S[k][j] for k, d in nz), zero) for j in range(r)])
-        M64 = np.array([[complex(x) for x in row] for row in M])
-        A_ = [M[i] + D[i] for i in range(r)]
-        for c in range(r):
-            p = max(range(c, r), key=lambda i: abs(A_[i][c]))
-            if A_[p][c] == 0:
-                return None
-            A_[c], A_[p] = A_[p], A_[c]
-            inv = 1 / A_[c][c]
-            rowc = [x * inv for x in A_[c][c:]]
-            A_[c][c:] = rowc
-            for i in range(r):
-                f = A_[i][c]
-                if i != c and f != 0:
-                    A_[i][c:] = [x - f * y for x, y in zip(A_[i][c:], rowc)]
-        ii, ll = _tri(r)
-        K = [A_[i][r + l] for i, l in zip(ii, ll)]
-        hi = np.array([complex(x) for x in K])
-        lo = np.array([complex(x - mp.mpc(h)) for x, h in zip(K, hi)])
-        return hi, lo, float(np.linalg.cond(M64))
-
-
 @functools.lru_cache(maxsize=None)
 def _reference(name):
     """The model's N_REF reference factors, computed once: (hi [n_tri, N_REF],
