@@ -747,7 +747,7 @@ __global__ void __launch_bounds__(kBlock) k_ev_lanes(pgw_ev_params p, pgw_ev_ste
       const int v = w * 64 + j;
       const bool in = ok && inw[w];
       r[i][w] = in ? (double)req[e * VP + v] : 0.0;
-      prev[i][w] = ok ? chg[(int64_t)w * n + e] : 0ull;
+      prev[i][w] = ok && w < s.n_words ? chg[(int64_t)w * n + e] : 0ull;   // (chg has n_words rows, not W)
       pw[i][w] = win[w];
       tlp[i][w] = tl[w];
       if constexpr (MODE == kEvPerEnv) {
@@ -800,7 +800,8 @@ __global__ void __launch_bounds__(kBlock) k_ev_lanes(pgw_ev_params p, pgw_ev_ste
     t.dcnt = dcnt;
     if (ok && j == 0) {
 #pragma unroll
-      for (int w = 0; w < W; ++w) chg[(int64_t)w * n + e] = now[w];
+      for (int w = 0; w < W; ++w)
+        if (w < s.n_words) chg[(int64_t)w * n + e] = now[w];
       ev_note(p, a[i]);
       (void)ev_finish(p, s, e, t, obs, rp, rew);
     }
