@@ -445,6 +445,9 @@ __device__ __forceinline__ double bld_std_step(const pgw_building_params& B, con
     return j < 5 ? T[j] - ub : j < 10 ? lb - T[j - 5] : j == 10 ? lb
          : j == 11 ? ub : j == 12 ? exn.T_oa : j == 13 ? pc : exn.time_of_day;
   };
+  // (obs_low[j] == obs_high[j]: c is the bound, the numerator an exact zero and
+  // exact_div returns 0 * (1 / 0) = NaN, as the generic path's 0 / 0 does --
+  // tests/test_gpu_comp_direct.py, "low-equals-high")
   if (B.rescale) {
 #pragma unroll
     for (int j = 0; j < 15; ++j) {
