@@ -383,7 +383,9 @@ typedef struct pgw_pf_tables {
  * SolveSnap -> DoNormalSolution, restated in oracle/pf_oracle.py
  * Feeder.snap_opendss) on pgw_pf_solve / pgw_coord_step's one-lane-per-env
  * kernels, for feeders of the fast shape (m = 14 constant-PQ elements, one
- * voltage band, at most one controllable slot): the packed block holds the
+ * voltage band; pgw_pf_solve / pgw_pf_solve_f32 with up to PGW_PF_MAX_CTRL
+ * controllable slots, pgw_coord_step and pgw_pf_od_probe with at most one):
+ * the packed block holds the
  * iteration matrix of Y + every load's nominal Yeq (W'' of that Y, u0 = the
  * direct solution C Y^-1 I_src); element k's current is I'_k = (conj(S_k) g -
  * y0'_k) u_k, y0' = the per-phase conj(S) whose Yeq sits in Y; the solve stops
@@ -409,7 +411,20 @@ typedef struct pgw_pf_tables {
  * start (device, this step's hour): the first iteration in closed form -- from
  * the direct solution the currents are affine in the env's controllable
  * (P, Q): u_1 = u1b + P u1P + Q u1Q and J_1 = J1b + P J1P + Q J1Q; u1b, u1P,
- * u1Q, J1b, J1P, J1Q (m complex each).
+ * u1Q, J1b, J1P, J1Q (m complex each).  With C = n_ctrl >= 2 slots
+ * (pgw_pf_solve, pgw_pf_solve_f32) the currents are affine in every slot's
+ * (P_s, Q_s),
+ *   u_1 = u1b + sum_s (P_s u1P_s + Q_s u1Q_s),
+ *   J_1 = J1b + sum_s (P_s J1P_s + Q_s J1Q_s)   (summed in slot order, P before Q),
+ * and start holds (4 + 8 C) m doubles: the one-slot table above for slot 0 in
+ * its place and layout -- [0, 12 m) --, then per slot s = 1 .. C-1 the four
+ * maps u1P_s, u1Q_s, J1P_s, J1Q_s (m complex each) at 12 m + 8 m (s - 1).
+ * J1P_s / J1Q_s are nonzero on the elements of slot s only (several elements
+ * may share a slot: a three-phase load).  Element k then draws
+ * ((base_kw[k] + ctrl_p[elem_ctrl[k]]) * 1000 / nph[k]) per lane, and every
+ * env runs the solve: with n_ctrl >= 2 it is no function of one kW, so resp,
+ * resp_v and resp_q must be NULL (PGW_ERR_ARG otherwise).  Check rows, bounds,
+ * sparse_envs, the stopping rule and the outputs do not depend on the slots.
  *
  * resp (device, this step's hour; NULL = every env runs the snap solve): the
  * RESPONSE TABLE of the hour's snap solve.  With one controllable slot and
@@ -467,7 +482,7 @@ typedef struct pgw_pf_od {
   int32_t sparse_envs;               /* 0 = default (4); < 0 never; <= 64     */
   const double* rows_V0;             /* n_rows complex (device)                */
   const double* rows_G;              /* n_rows x m complex (device)            */
-  const double* start;               /* 12 m doubles (device)                  */
+  const double* start;               /* (4 + 8 max(n_ctrl, 1)) m doubles (device): 12 m with one slot */
   const double* resp;                /* response table records (device) or NULL */
   double resp_x0, resp_h;            /* grid origin and step (kW)               */
   int32_t resp_nseg;                 /* grid segments (primary records)         */
@@ -491,7 +506,11 @@ typedef struct pgw_pf_od {
  * ctrl_p / ctrl_q: n_ctrl x n (kW / kvar, NULL = 0).  v_out: n_out x n (pu); NULL
  * when only the extrema (pgw_pf_tables.v_min_out / v_max_out) are wanted.
  * iters: n (int32, nullable) iteration count per env; -count when the env stopped
- * at max_iter without passing the convergence test. */
+ * at max_iter without passing the convergence test.
+ * With t->od set (OpenDSS's rule on the fast kernels, pgw_pf_od above): m = 14,
+ * one voltage band, no load_scale and no U_init; n_ctrl <= 1 reads the
+ * response table where there is one, 2 <= n_ctrl <= PGW_PF_MAX_CTRL solves
+ * every env from the multi-slot start table and takes no response table. */
 int32_t pgw_pf_solve(const pgw_pf_params* p, const pgw_pf_tables* t, int64_t n,
                      const double* ctrl_p, const double* ctrl_q, double* v_out,
                      int32_t* iters, void* stream);

@@ -115,6 +115,7 @@ template <int M, bool UB, bool GC> struct PFSolver {
   double sr[GC ? M : 1], si[GC ? M : 1];
   double pc, qc;           // slot-0 controllable kW / kvar of the env
   double lo2, mn2, mx2, tol2;
+  static constexpr bool kMulti = false;   // (od_solve: see PFSolverMS)
 
   __device__ __forceinline__ void load(const PFArgs& a, const double* block) {
     const int l = threadIdx.x & 15;
@@ -1122,7 +1123,8 @@ __global__ void __launch_bounds__(kBlock) k_coord_pf(CoordPFArgs c, PFArgs a, pg
 // (pgw_pf_od, include/pgw.h): the reference's own stopping rule on the fast
 // one-lane-per-env kernels.  Per env, from the direct solution u0:
 //   iteration 1   u_1 = u1b + P u1P + Q u1Q (the currents at u0 are affine in
-//                 the env's controllable P, Q: the host's per-hour table);
+//                 the env's controllable P, Q: the host's per-hour table; with
+//                 several slots the sum over every slot's, od_first_ms);
 //   iteration k   J = I'(u_{k-1}) (compensation currents), u_k = u0 + W'' J --
 //                 the resident DPP matvec of the exact solve;
 //   test          max over every node of | |V_k| - |V_{k-1}| | <= tol from
@@ -1470,8 +1472,12 @@ __device__ __forceinline__ void od_load_J(const ODShared<M>& sh, int it, double 
 // currents it forms (u_1 .. u_{k*-1}), then the returned count: a 64-bit FNV-1a
 // style hash that tells the smooth pieces of the solve as a function of P apart.
 constexpr uint64_t kFnvBasis = 0xcbf29ce484222325ull, kFnvPrime = 0x100000001b3ull;
-template <int M, bool SIG = false>
-__device__ int od_solve(PFSolver<M, true, false>& S, const ODArgs& o, const ODStage<M>& g, bool valid,
+// SV: the lane's solver -- PFSolver<M, true, false> (one controllable slot), or
+// PFSolverMS<M> (several: k_pf_solve_od_ms), whose caller has run iteration 1
+// (od_first_ms: u_1 in S, J_1 in sh.J[1]) and whose current law reads the
+// lane's own element powers; everything from iteration 2 on is the same code.
+template <int M, bool SIG = false, class SV = PFSolver<M, true, false>>
+__device__ int od_solve(SV& S, const ODArgs& o, const ODStage<M>& g, bool valid,
                         ODShared<M>& sh, uint64_t* sig = nullptr) {
   static_assert(kOdRows <= 2 * M, "od_rows keeps two row magnitudes per current slot");
   const int tid = threadIdx.x;
@@ -1498,9 +1504,11 @@ __device__ int od_solve(PFSolver<M, true, false>& S, const ODArgs& o, const ODSt
       sh.J[1][k * kBlock + tid] = make_double2(jr, ji);
     }
   };
+  if constexpr (!SV::kMulti) {
 #pragma unroll
-  for (int k = 0; k < M; ++k) affine(k, S.ur[k], S.ui[k]);
-  if (o.max_iter <= 1) currents_1();                 // (uniform)
+    for (int k = 0; k < M; ++k) affine(k, S.ur[k], S.ui[k]);
+    if (o.max_iter <= 1) currents_1();               // (uniform)
+  }
   int it = 1, my_it = 1;
   bool done = !valid || o.max_iter <= 1, conv_ok = !valid;
   while (__ballot(!done) != 0ull) {
@@ -1586,7 +1594,9 @@ __device__ int od_solve(PFSolver<M, true, false>& S, const ODArgs& o, const ODSt
     }
     int d = 0;
     if (exact) {
-      if (it == 2) currents_1();                     // (uniform)
+      if constexpr (!SV::kMulti) {
+        if (it == 2) currents_1();                   // (uniform)
+      }
       // the change bound's sums: this iteration's currents against the
       // previous ones (the rounding, ~1e-15 relative, as slack)
       double dsum = 0.0, jsum = 0.0;
@@ -2916,6 +2926,195 @@ __global__ void __launch_bounds__(kBlock) k_pf_solve_od(PFArgs a, ODArgs o, pgw_
   if (iters) iters[e] = it;
 }
 
+// ---- several controllable slots (2 <= n_ctrl <= PGW_PF_MAX_CTRL) -----------
+// The snap solve above with per-lane powers for every element: element k draws
+// ((base_kw[k] + P_s) 1000 / nph[k]) for its slot s = elem_ctrl[k] (k_pf_solve's
+// GC form, the operations of PFSolver::powers), kept per lane for the whole
+// solve -- 2 M doubles, which fit the register file (the resource figures are
+// in DESIGN.md section 8) because this kernel has no response-table lookup: the
+// solve is not a function of one kW, so every env runs it.  One instantiation
+// serves every slot count; nothing below iteration 1 sees the slots.
+template <int M> struct PFSolverMS : PFSolver<M, true, false> {
+  static constexpr bool kMulti = true;
+  double msr[M], msi[M];   // the env's conj(S_k) per phase (W, -var)
+
+  __device__ __forceinline__ void powers_ms(const PFArgs& a, const double (&cp)[PGW_PF_MAX_CTRL],
+                                            const double (&cq)[PGW_PF_MAX_CTRL]) {
+#pragma unroll
+    for (int k = 0; k < M; ++k) {
+      const int c = a.ctrl[k];                       // (uniform)
+      double p = 0.0, q = 0.0;
+#pragma unroll
+      for (int s = 0; s < PGW_PF_MAX_CTRL; ++s) {
+        p = (c == s) ? cp[s] : p;
+        q = (c == s) ? cq[s] : q;
+      }
+      msr[k] = ((a.kw[k] + p) * 1000.0) / a.nph[k];
+      msi[k] = -(((a.kvar[k] + q) * 1000.0) / a.nph[k]);
+    }
+  }
+
+  // PFSolver::current_od with the lane's own element power
+  template <int K>
+  __device__ __forceinline__ void current_od(double y0r, double y0i, double& ir, double& ii) const {
+    const double s_r = msr[K], s_i = msi[K];
+    const double m2 = fma(this->ui[K], this->ui[K], this->ur[K] * this->ur[K]);
+    double mc = fmin(fmax(m2, this->mn2), this->mx2);
+    mc = (m2 <= this->lo2) ? 1.0 : mc;
+    const double g = fast_rcp(mc);
+    const double cr = fma(s_r, g, -y0r), ci = fma(s_i, g, -y0i);
+    ir = fma(cr, this->ur[K], -(ci * this->ui[K]));
+    ii = fma(cr, this->ui[K], ci * this->ur[K]);
+  }
+};
+
+// The first-iteration table of C slots (pgw_pf_od.start, (4 + 8 C) M doubles):
+// the one-slot table [0, 12 M) -- slot 0's -- in ODShared::st, then per further
+// slot s its u1P_s, u1Q_s, J1P_s, J1Q_s (M complex each) in ext.
+template <int M> struct ODSharedMS {
+  static constexpr int kExt = 8 * (PGW_PF_MAX_CTRL - 1) * M;
+  ODShared<M> base;
+  double ext[kExt];
+};
+template <int M> struct ODStageMS {
+  static constexpr int kExtQ = (ODSharedMS<M>::kExt + kBlock - 1) / kBlock;
+  ODStage<M> base;
+  double x[kExtQ];
+};
+template <int M>
+__device__ __forceinline__ void od_stage_load_ms(const ODArgs& o, int n_ctrl, ODStageMS<M>& g) {
+  od_stage_load<M>(o, o.start, g.base);
+  const int total = 8 * (n_ctrl - 1) * M;            // (uniform; the table's extent past 12 M)
+#pragma unroll
+  for (int q = 0; q < ODStageMS<M>::kExtQ; ++q) {
+    const int i = threadIdx.x + q * kBlock;
+    g.x[q] = i < total ? o.start[12 * M + i] : 0.0;
+  }
+}
+template <int M>
+__device__ __forceinline__ void od_stage_store_ms(const ODArgs& o, const ODStageMS<M>& g, ODSharedMS<M>& sh) {
+  od_stage_store<M>(o, g.base, sh.base);
+#pragma unroll
+  for (int q = 0; q < ODStageMS<M>::kExtQ; ++q) {
+    const int i = threadIdx.x + q * kBlock;
+    if (i < ODSharedMS<M>::kExt) sh.ext[i] = g.x[q];
+  }
+}
+
+// Iteration 1 in closed form (the table staged and synchronised): from the
+// direct solution the currents are affine in every slot's (P, Q),
+//   u_1 = u1b + sum_s (P_s u1P_s + Q_s u1Q_s),  J_1 = J1b + sum_s (P_s J1P_s + Q_s J1Q_s),
+// accumulated slot by slot, P before Q (with one slot: od_solve's affine(), bit
+// for bit).  u_1 goes to S, J_1 to the lane's sh.J[1] slots -- where iteration 2
+// expects the previous currents, and the outputs' input when max_iter = 1.
+template <int M>
+__device__ __forceinline__ void od_first_ms(PFSolverMS<M>& S, int n_ctrl, const double (&cp)[PGW_PF_MAX_CTRL],
+                                            const double (&cq)[PGW_PF_MAX_CTRL], ODSharedMS<M>& sh) {
+  const double* st = sh.base.st;
+  double jr[M], ji[M];
+#pragma unroll
+  for (int k = 0; k < M; ++k) {
+    S.ur[k] = st[2 * k];
+    S.ui[k] = st[2 * k + 1];
+    jr[k] = st[2 * (3 * M + k)];
+    ji[k] = st[2 * (3 * M + k) + 1];
+  }
+  static_for<0, PGW_PF_MAX_CTRL>([&](auto ss) {
+    constexpr int s = decltype(ss)::value;
+    if (s < n_ctrl) {                                // (uniform)
+      // slot 0: the one-slot layout (J1b lies between its u and J parts)
+      const double* tu = s == 0 ? st + 2 * M : sh.ext + (s - 1) * 8 * M;
+      const double* tj = s == 0 ? st + 8 * M : sh.ext + (s - 1) * 8 * M + 4 * M;
+      const double P = cp[s], Q = cq[s];
+#pragma unroll
+      for (int k = 0; k < M; ++k) {
+        S.ur[k] = fma(Q, tu[2 * (M + k)], fma(P, tu[2 * k], S.ur[k]));
+        S.ui[k] = fma(Q, tu[2 * (M + k) + 1], fma(P, tu[2 * k + 1], S.ui[k]));
+        jr[k] = fma(Q, tj[2 * (M + k)], fma(P, tj[2 * k], jr[k]));
+        ji[k] = fma(Q, tj[2 * (M + k) + 1], fma(P, tj[2 * k + 1], ji[k]));
+      }
+    }
+  });
+#pragma unroll
+  for (int k = 0; k < M; ++k) sh.base.J[1][k * kBlock + threadIdx.x] = make_double2(jr[k], ji[k]);
+}
+
+// pgw_pf_solve, OpenDSS rule, 2 .. PGW_PF_MAX_CTRL controllable slots:
+// k_pf_solve_od's prologue and outputs around the solve of every env (no
+// response table).
+template <int M, class IO = double>
+__global__ void __launch_bounds__(kBlock) k_pf_solve_od_ms(PFArgs a, ODArgs o, pgw_pf_tables t, int64_t n,
+                                                           const IO* __restrict__ ctrl_p,
+                                                           const IO* __restrict__ ctrl_q,
+                                                           IO* __restrict__ v_out,
+                                                           int32_t* __restrict__ iters) {
+  const int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  const bool valid = e < n;
+  __shared__ ODSharedMS<M> sh;
+  ODStageMS<M> stg;
+  const bool rows_lds = od_rows_lds<M>(a.n_out);     // (uniform)
+  PFSolverMS<M> S;
+  // the solve's operands first, in flight with the env's powers
+  od_stage_load_ms<M>(o, a.n_ctrl, stg);
+  S.load(a, t.block);
+  double cp[PGW_PF_MAX_CTRL], cq[PGW_PF_MAX_CTRL];
+#pragma unroll
+  for (int c = 0; c < PGW_PF_MAX_CTRL; ++c) {
+    cp[c] = (valid && c < a.n_ctrl && ctrl_p) ? (double)ctrl_p[(int64_t)c * n + e] : 0.0;
+    cq[c] = (valid && c < a.n_ctrl && ctrl_q) ? (double)ctrl_q[(int64_t)c * n + e] : 0.0;
+  }
+  S.powers_ms(a, cp, cq);
+  od_stage_store_ms<M>(o, stg, sh);
+  __syncthreads();                                   // the staged check rows and table
+  od_first_ms<M>(S, a.n_ctrl, cp, cq, sh);
+  int it = 0;
+  if (__ballot(valid) != 0ull)                       // (wave-uniform) some env of this wave
+    it = od_solve<M, false, PFSolverMS<M>>(S, o, stg.base, valid, sh.base);
+  // the output rows' loads only now: in flight through the solve (as
+  // k_pf_solve_od issues them) their 16 doubles per lane, on top of the
+  // per-lane element powers, no longer fit the 512 registers (12 bytes of
+  // scratch per lane); here they overlap node 0 and the element-voltage stores
+  double rv[kOdRowQ];
+  if (rows_lds) od_rows_issue<M>(t, a.n_out, rv);
+  double ir[M], ii[M], v0r = 0.0, v0i = 0.0;
+  od_load_J<M>(sh.base, it, ir, ii);
+  pf_node0<M>(v0r, v0i, S.w, ir, ii);
+  const double m2_0 = fma(v0i, v0i, v0r * v0r);
+  const double v0 = sqrt(m2_0);
+  if (valid && t.U_out) {
+#pragma unroll
+    for (int k = 0; k < M; ++k) {
+      t.U_out[2 * (e * M + k)] = S.ur[k];
+      t.U_out[2 * (e * M + k) + 1] = S.ui[k];
+    }
+  }
+  double vmn = v0, vmx = v0;      // Python min()/max() over the rows in order
+  const double* srow = rows_lds ? od_rows_put<M>(sh.base, a.n_out, rv) : nullptr;
+  if (v_out || !rows_lds) {
+    pf_rows_out<M>(t, rows_lds, srow, a.n_out, ir, ii, [&](int ro, double v) {
+      if (valid && v_out) v_out[(int64_t)ro * n + e] = (IO)v;
+      vmn = (v < vmn) ? v : vmn;
+      vmx = (v > vmx) ? v : vmx;
+    });
+  } else {
+    // extrema only (as k_pf_solve_od)
+    double mn2 = m2_0, mx2 = mn2;
+    pf_rows_out<M, false>(t, rows_lds, srow, a.n_out, ir, ii, [&](int, double m2) {
+      mn2 = (m2 < mn2) ? m2 : mn2;
+      mx2 = (m2 > mx2) ? m2 : mx2;
+    });
+    vmn = sqrt(mn2);
+    vmx = sqrt(mx2);
+  }
+  if (!valid) return;
+  if (a.n_out > 0) {
+    if (v_out) v_out[e] = (IO)v0;
+    if (t.v_min_out) t.v_min_out[e] = vmn;
+    if (t.v_max_out) t.v_max_out[e] = vmx;
+  }
+  if (iters) iters[e] = it;
+}
+
 // Response-table builder (pgw_pf_od_probe): the snap solve at lane e's kW P[e]
 // (Q = 0) in hour e / lanes_per_hour -- that hour's PFArgs (base loads) and
 // first-iteration table -- with the signature of its pieces.
@@ -3210,11 +3409,17 @@ __global__ void __launch_bounds__(kBlock) k_band_penalty(int64_t n, const double
 }
 
 // OpenDSS rule on the fast kernels (pgw_pf_tables.od): the C4 shape only.
-static int32_t check_od(const pgw_pf_params& p, const pgw_pf_tables& t, const char* who) {
+// max_ctrl: the slots the caller's kernels take (pgw_pf_solve: PGW_PF_MAX_CTRL,
+// k_pf_solve_od_ms beyond one; the fused C4 step and the probe: one).
+static int32_t check_od(const pgw_pf_params& p, const pgw_pf_tables& t, const char* who, int max_ctrl = 1) {
   const pgw_pf_od* d = t.od;
-  PGW_REQUIRE(p.m == 14 && uniform_band(p) && p.n_ctrl <= 1 && !t.load_scale && !t.U_init,
-              "%s: the OpenDSS fast path needs m = 14, one voltage band, <= 1 controllable slot and no "
-              "load_scale / U_init (use pgw_pf_solve_general)", who);
+  PGW_REQUIRE(p.m == 14 && uniform_band(p) && p.n_ctrl <= max_ctrl && !t.load_scale && !t.U_init,
+              "%s: the OpenDSS fast path needs m = 14, one voltage band, <= %d controllable slot(s) and no "
+              "load_scale / U_init (use pgw_pf_solve_general)", who, max_ctrl);
+  // several slots: the solve is not a function of one kW, so no response table
+  PGW_REQUIRE(p.n_ctrl <= 1 || (!d->resp && !d->resp_v && !d->resp_q),
+              "%s: %d controllable slots take no response table (od resp / resp_v / resp_q must be NULL)", who,
+              p.n_ctrl);
   PGW_REQUIRE(d->n_rows >= 0 && d->n_rows <= PGW_PF_OD_MAX_ROWS && d->n_rep >= 0 && d->n_rep <= d->n_rows,
               "%s: od n_rep %d / n_rows %d (<= %d)", who, d->n_rep, d->n_rows, PGW_PF_OD_MAX_ROWS);
   PGW_REQUIRE(d->start && (d->n_rows == 0 || (d->rows_V0 && d->rows_G)), "%s: od start / rows missing", who);
@@ -3718,11 +3923,16 @@ static int32_t pf_solve(const pgw_pf_params* p, const pgw_pf_tables* t, int64_t 
               "pgw_pf_solve: n_out > 0 but no output (v_out, v_min_out, v_max_out all NULL)");
   PGW_REQUIRE(p->max_iter >= 1, "pgw_pf_solve: max_iter < 1");
   if (t->od) {
-    const int32_t rc = check_od(*p, *t, "pgw_pf_solve");
+    const int32_t rc = check_od(*p, *t, "pgw_pf_solve", PGW_PF_MAX_CTRL);
     if (rc) return rc;
   }
   if (n == 0) return PGW_OK;
   const PFArgs a = make_pf_args(*p, *t);
+  if (t->od && p->n_ctrl > 1) {
+    launch_timed(PGW_T_PF_SOLVE, k_pf_solve_od_ms<14, IO>, dim3(grid_for(n)), dim3(kBlock), (hipStream_t)stream,
+                 a, make_od_args(*t->od, p->max_iter), *t, n, ctrl_p, ctrl_q, v_out, iters);
+    return check_launch("k_pf_solve_od_ms");
+  }
   if (t->od) {
     launch_timed(PGW_T_PF_SOLVE, k_pf_solve_od<14, IO>, dim3(grid_for(n)), dim3(kBlock), (hipStream_t)stream, a,
                  make_od_args(*t->od, p->max_iter), *t, n, ctrl_p, ctrl_q, v_out, iters);

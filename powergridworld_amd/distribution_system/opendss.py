@@ -90,6 +90,48 @@ def extrema_candidates_per_piece(A, B, C, tl, th, samples=9, delta=1e-9):
     return cand
 
 
+def od_start_affine(W2, u0, nph, elem_ctrl, n_slots, band2):
+    """The hour-independent part of the first-iteration table (pgw_pf_od.start):
+    from the direct solution u0 the compensation currents are affine in every
+    controllable slot's (P, Q) -- g(|u0|^2) is the same for every env --, so per
+    slot s the maps jP_s, jQ_s (the currents' change per kW / kvar: nonzero on
+    the slot's elements) and u1P_s = W'' jP_s, u1Q_s = W'' jQ_s.  Pure NumPy.
+    W2 [M, M], u0 [M] complex (pu); nph, elem_ctrl [M]; band2 = (vlow^2,
+    vmin^2, vmax^2).  Returns (g [M], [(u1P, u1Q, jP, jQ)] per slot)."""
+    lo2, mn2, mx2 = band2
+    nph = np.asarray(nph, float)
+    ctrl = np.asarray(elem_ctrl)
+    m2 = np.abs(u0) ** 2
+    g = 1.0 / np.where(m2 <= lo2, 1.0, np.clip(m2, mn2, mx2))
+    slots = []
+    for s in range(n_slots):
+        on = ctrl == s
+        fr = np.where(on, 1000.0 / nph, 0.0)
+        fi = np.where(on, -1000.0 / nph, 0.0)
+        jP, jQ = fr * g * u0, 1j * fi * g * u0
+        slots.append((W2 @ jP, W2 @ jQ, jP, jQ))
+    return g, slots
+
+
+def od_start_table(W2, u0, y0, base_kw, base_kvar, nph, affine):
+    """pgw_pf_od.start of one hour for C = len(slots) controllable slots, (4 +
+    8 C) M doubles: u1b, u1P_0, u1Q_0, J1b, J1P_0, J1Q_0 -- the one-slot table
+    and layout, 12 M -- then u1P_s, u1Q_s, J1P_s, J1Q_s per further slot (M
+    complex each), so that
+        u_1 = u1b + sum_s (P_s u1P_s + Q_s u1Q_s),  J_1 = J1b + sum_s (P_s J1P_s + Q_s J1Q_s).
+    base_kw / base_kvar [M]: the hour's base loads per element; y0 [M] complex:
+    the loads' Yeq powers; affine: od_start_affine's result.  Pure NumPy."""
+    g, slots = affine
+    nph = np.asarray(nph, float)
+    s0 = (np.asarray(base_kw, float) * 1000.0) / nph - 1j * ((np.asarray(base_kvar, float) * 1000.0) / nph)
+    J0 = (s0 * g - y0) * u0
+    u1P, u1Q, jP, jQ = slots[0]
+    parts = [u0 + W2 @ J0, u1P, u1Q, J0, jP, jQ]
+    for sl in slots[1:]:
+        parts.extend(sl)
+    return np.concatenate(parts).view(np.float64)
+
+
 class OpenDSSSolver(PowerFlowSolver):
 
     # Per-hour predictor grid (single controllable load): the batched solve
@@ -110,7 +152,7 @@ class OpenDSSSolver(PowerFlowSolver):
                  output_nodes=None, predictor: bool = True, warm_start: bool = False,
                  convergence: str = "opendss", general: bool = None, od_table: bool = True,
                  snap_start: str = "direct", yprim: str = "dss_file", control_loop: str = "host",
-                 **kwargs):
+                 multi_bus: str = "general", **kwargs):
         """convergence: "opendss" (the default) -- OpenDSS's own snap solve as
         the reference runs it (opendss.py:134):
         loads' nominal admittances in Y, start from the direct solution, stop at
@@ -146,8 +188,18 @@ class OpenDSSSolver(PowerFlowSolver):
         passes), no synchronisation, the same per-env arithmetic and results
         bit for bit; control_passes then holds each env's solves, and the
         fused multi-agent step (pgw_ma_step) serves the feeder.  Not with
-        snap_start="previous" on such a feeder (ValueError)."""
+        snap_start="previous" on such a feeder (ValueError).
+        multi_bus (OpenDSS rule, 2 .. 8 controllable loads on a feeder of the
+        fast shape; nothing changes otherwise): "general" (the default) -- the
+        general kernel, as every other feeder; "fast" -- the fast kernel's
+        multi-slot instantiation (k_pf_solve_od_ms: per-lane element powers,
+        the closed-form first iteration over every slot, no response table --
+        od_table is ignored there, every env is solved), which the fused
+        multi-agent step then runs too; `general` / `_od_fast` tell which."""
         super().__init__(**kwargs)
+        if multi_bus not in ("general", "fast"):
+            raise ValueError("multi_bus must be 'general' or 'fast', got %r" % (multi_bus,))
+        self.multi_bus = multi_bus
         if control_loop not in ("host", "device"):
             raise ValueError("control_loop must be 'host' or 'device', got %r" % (control_loop,))
         self.control_loop = control_loop
@@ -183,7 +235,8 @@ class OpenDSSSolver(PowerFlowSolver):
         model1 = not bool((f.elem_model != 1).any())
         # OpenDSS's rule on the fast kernels (pgw_pf_tables.od): the C4 shape --
         # 14 constant-PQ elements in one voltage band, no RegControl; at most one
-        # controllable load (set_controllable_loads falls back beyond that)
+        # controllable load, or with multi_bus="fast" up to 8
+        # (set_controllable_loads falls back to the general kernel beyond that)
         self._od_fast = (convergence == "opendss" and not general and not regctl and model1 and
                          self.OPENDSS_MIN_ITER >= 2 and
                          f.m <= _lib.PF_MAX_M and int(_lib.lib().pgw_pf_padded_m(f.m)) == 14 and
@@ -405,26 +458,23 @@ class OpenDSSSolver(PowerFlowSolver):
         W2, u0 = self._od_W2, self._od_u0
         p0 = self.params
         nph = np.array(p0.nph[:M])
-        ctrl0 = np.array(p0.elem_ctrl[:M]) == 0
-        fr = np.where(ctrl0, 1000.0 / nph, 0.0)
-        fi = np.where(ctrl0, -1000.0 / nph, 0.0)
         y0 = np.array(od.y0r[:M]) + 1j * np.array(od.y0i[:M])
-        m2 = np.abs(u0) ** 2
-        lo2, mn2, mx2 = p0.vlow[0] ** 2, p0.vmin[0] ** 2, p0.vmax[0] ** 2
-        g = 1.0 / np.where(m2 <= lo2, 1.0, np.clip(m2, mn2, mx2))
-        jP, jQ = fr * g * u0, 1j * fi * g * u0
-        u1P, u1Q = W2 @ jP, W2 @ jQ
-        recs = np.zeros((len(hours), self._od_start.shape[1]))
+        # one table per slot set: (4 + 8 C) M doubles, 12 M with one slot (or none)
+        n_slots = max(len(self._ctrl_names), 1)
+        width = (4 + 8 * n_slots) * M
+        if self._od_start.shape[1] != width:     # (the slots changed: _base_params emptied the index)
+            self._od_start = torch.zeros((self.OD_MAX_TABLES, width), dtype=torch.float64, device=self.device)
+        affine = od_start_affine(W2, u0, nph, np.array(p0.elem_ctrl[:M]), n_slots,
+                                 (p0.vlow[0] ** 2, p0.vmin[0] ** 2, p0.vmax[0] ** 2))
+        recs = np.zeros((len(hours), width))
         for q, h in enumerate(hours):
             p = self._params_for_hour(h)
-            s0 = (np.array(p.base_kw[:M]) * 1000.0) / nph - 1j * ((np.array(p.base_kvar[:M]) * 1000.0) / nph)
-            J0 = (s0 * g - y0) * u0
-            recs[q] = np.concatenate([u0 + W2 @ J0, u1P, u1Q, J0, jP, jQ]).view(np.float64)
+            recs[q] = od_start_table(W2, u0, y0, np.array(p.base_kw[:M]), np.array(p.base_kvar[:M]), nph, affine)
         for j, k in enumerate(keys):
             self._od_index[k] = idx0 + j
         if hours:
             self._od_start[idx0:idx0 + len(hours)].copy_(torch.from_numpy(recs), non_blocking=False)
-            if self.od_table:
+            if self.od_table and n_slots == 1:   # (several slots: no response table, every env is solved)
                 self._od_response(hours, idx0)
 
     # ------------------------------------------------------------ OpenDSS rule: response tables
@@ -870,7 +920,7 @@ class OpenDSSSolver(PowerFlowSolver):
         od = _lib.PFOD.from_buffer_copy(self._od_proto)
         od.start = self._od_start[idx].data_ptr()
         od.resp_v_row = -1
-        if self.od_table and self._od_resp is not None:
+        if self.od_table and self._od_resp is not None and len(self._ctrl_names) <= 1:
             od.resp = self._od_resp[idx].data_ptr()
             od.resp_x0, od.resp_h, od.resp_nseg = self.PREDICTOR_X0, self.PREDICTOR_H, self.PREDICTOR_N - 1
             od.resp_rows = self._od_row_mask(idx) if self.od_row_masks else 0
@@ -1128,8 +1178,10 @@ class OpenDSSSolver(PowerFlowSolver):
         if names != self._ctrl_names:
             self._ctrl_names = names
             self._seen_keys = None
-            if self._od_fast and len(names) > 1:
-                # the fast OpenDSS kernels take one controllable slot: the general kernel
+            if self._od_fast and len(names) > 1 and self.multi_bus != "fast":
+                # several controllable slots run the general kernel unless
+                # multi_bus="fast" asks for the fast kernel's multi-slot
+                # instantiation (k_pf_solve_od_ms: no response table)
                 self._od_fast, self.general = False, True
                 self.set_output_nodes(self.output_names)
             else:

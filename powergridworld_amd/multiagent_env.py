@@ -413,6 +413,10 @@ class MultiAgentEnv(Env):
             return "snap_start='previous' (each env's solve starts from its own previous solution)"
         if getattr(self.pf_solver, "yprim", "dss_file") != "dss_file":
             return "yprim='step' (every solve's Y holds its own loads' admittances)"
+        if getattr(self.pf_solver, "multi_bus", "general") == "fast" and self.pf_solver._od_fast and \
+                len(set(b for b in self.agent_name_bus_map.values() if b in self.pf_solver.load_bus_name)) > 1:
+            # pgw_coord_step's OpenDSS-rule kernels take one controllable slot
+            return "multi_bus='fast' with agents on several buses (pgw_ma_step runs the multi-slot power flow)"
         if len(self.agents) > _lib.MAX_AGENTS:
             return "more than %d agents" % _lib.MAX_AGENTS
         cls = type(self)

@@ -10,7 +10,10 @@ Usage: python tools/bench_configs.py [--configs C2,C3,HET,HETG,HS,...] [--steps 
 (HET: OpenDSS's snap-solve rule, the default, with its response table; HETS:
 every env solved; HETX: the exact fixed point; HETG: the heterogeneous scenario
 on the generic path, fused=False; HETF: HET with fp32 storage
-(pgw_ma_step_f32); C3F / C3G8F:
+(pgw_ma_step_f32); HETMG / HETMF: the heterogeneous agents on three buses
+(675c, 634a, 684c), the power flow on the general kernel (multi_bus="general",
+the default route) / on the fast kernel's multi-slot instantiation
+(multi_bus="fast"); C3F / C3G8F:
 C3 with fp32 storage (pgw_mc_agent_step_f32); C3L: C3 at
 65 536 envs; C2Gk / C3Gk: the step replayed from captured hipGraphs of k steps,
 C3 through the device clocks; C3Pk / HSPk: captured once per episode position,
@@ -29,6 +32,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 # algorithmic HBM bytes per agent-env-step
 BYTES = {"C2": 48, "C3": 1990}
+# HETMG / HETMF: the heterogeneous agents' buses (building, PV farm, EV station)
+MULTI_BUSES = ("675c", "634a", "684c")
 
 
 def timed_loop(env, step, reset, steps, warmup):
@@ -147,10 +152,16 @@ def bench_c3(dev, steps, warmup, n=16384, pool=16, graph=0, clocked=True, dtype=
 
 
 def bench_het(dev, steps, warmup, n=65536, pool=16, fused="auto", conv="opendss", table=True, vrec=True, qrec=True,
-              rrows=True, dtype=torch.float64):
+              rrows=True, dtype=torch.float64, multi_bus=None):
     from powergridworld_amd.scenarios.heterogeneous import make_env_config
     from powergridworld_amd.multiagent_env import MultiAgentEnv
-    env = MultiAgentEnv(**make_env_config(pf_convergence=conv), num_envs=n, device=dev, fused=fused, dtype=dtype)
+    cfg = make_env_config(pf_convergence=conv)
+    if multi_bus:                  # one bus per agent; several controllable slots take no response table
+        for a, bus in zip(cfg["agents"], MULTI_BUSES):
+            a["bus"] = bus
+        cfg["pf_config"]["config"]["multi_bus"] = multi_bus
+        table = False
+    env = MultiAgentEnv(**cfg, num_envs=n, device=dev, fused=fused, dtype=dtype)
     env.pf_solver.od_table = table
     if hasattr(env.pf_solver, "od_node_records"):
         env.pf_solver.od_node_records = vrec
@@ -175,13 +186,18 @@ def bench_het(dev, steps, warmup, n=65536, pool=16, fused="auto", conv="opendss"
         return dones["__all__"]
 
     dt = timed_loop(env, step, env.reset, steps, warmup)
-    return dict(config=("HET" if fused else "HETG") + ("X" if conv == "exact" else "") + ("" if table else "S")
-                + ("" if vrec else "V") + ("" if qrec else "Q") + ("" if rrows else "R")
-                + ("F" if dtype == torch.float32 else ""),
-                workload="3-agent heterogeneous (MC building, grid-aware PV farm, EV 25x40) + IEEE-13 PF, "
+    name = ("HET" if fused else "HETG") + ("X" if conv == "exact" else "") + ("" if table else "S") \
+        + ("" if vrec else "V") + ("" if qrec else "Q") + ("" if rrows else "R") \
+        + ("F" if dtype == torch.float32 else "")
+    if multi_bus:
+        name = "HETM" + multi_bus[0].upper()
+    return dict(config=name,
+                workload="3-agent heterogeneous (MC building, grid-aware PV farm, EV 25x40)"
+                         + (" on buses %s" % ", ".join(MULTI_BUSES) if multi_bus else "") + " + IEEE-13 PF, "
                          + ("fused multi-agent step (pgw_ma_step%s)" % ("_f32" if dtype == torch.float32 else "")
                             if env._ma is not None else "generic path"),
                 pf_convergence=conv, pf_response_table=bool(table and conv == "opendss"),
+                pf_kernel="general" if env.pf_solver.general else "fast",
                 batch=n, agents=3, steps=steps, seconds=dt)
 
 
@@ -237,6 +253,8 @@ def main():
            "HETQ": lambda *a: bench_het(*a, qrec=False),
            "HETR": lambda *a: bench_het(*a, rrows=False),
            "HETF": lambda *a: bench_het(*a, dtype=torch.float32),
+           "HETMG": lambda *a: bench_het(*a, multi_bus="general"),
+           "HETMF": lambda *a: bench_het(*a, multi_bus="fast"),
            "C2G1": lambda *a: bench_c2(*a, graph=1), "C2G8": lambda *a: bench_c2(*a, graph=8),
            "C3G1": lambda *a: bench_c3(*a, graph=1), "C3G8": lambda *a: bench_c3(*a, graph=8),
            "C3P1": lambda *a: bench_c3(*a, graph=1, clocked=False),
