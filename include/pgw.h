@@ -522,6 +522,51 @@ int32_t pgw_pf_solve_f32(const pgw_pf_params* p, const pgw_pf_tables* t, int64_t
                          const float* ctrl_p, const float* ctrl_q, float* v_out,
                          int32_t* iters, void* stream);
 
+/* OpenDSS's snap solve in the reading where every solve's Y holds its own
+ * loads' Yeq (OpenDSSSolver yprim="step", H1; oracle/pf_oracle.py
+ * Feeder.snap_opendss with yprim_kw = None) on the fast one-lane-per-env
+ * kernel, for feeders of the fast shape (m = 14 constant-PQ elements, one
+ * voltage band) whose controllable load, if any, is ONE load phase element c.
+ * The map, against pgw_pf_od above: t carries the HOUR's reduction -- with dD
+ * the hour's base-load Yeq change against the DSS file's (per element, W - j
+ * var per phase), W_h = (I - W'' dD)^-1 W'' and u0_h = (I - W'' dD)^-1 u0 in
+ * t->block (pgw_pf_pack, with output row 0), and every row V0 + G J' of the
+ * file model as V0_h + G_h J', G_h = G (I + dD W_h), V0_h = V0 + G dD u0_h, in
+ * t->G / t->V0 (the output rows) and t->od->rows_V0 / rows_G (the check rows:
+ * n_rep = n_rows evaluates every one; bounded rows need gamma, eps, gmax, gsrc
+ * of the hour's rows).  Of t->od the entry reads tol, min_iter, elem_scale,
+ * the rows and sparse_envs; y0r / y0i and start are not read (y0' is the
+ * step's own power, and there is no first-iteration table); resp, resp_v and
+ * resp_q must be NULL.  Per env, with d = (P 1000 / nph_c, -(Q 1000 / nph_c))
+ * its controllable conj(S) per phase and K = d / (1 - d W_h[c,c]):
+ *   start        u = u0_h + W_h[:, c] K u0_h[c] (the direct solution at the
+ *                env's own Y);
+ *   iteration    J'_k = (s_k g_k - s_k) u_k for every element (s_k the step's
+ *                own conj(S) per phase, g pgw_pf_od's band law),
+ *                raw = u0_h + W_h J', cc = K raw[c], u_new = raw + W_h[:, c] cc,
+ *                J_eff = J' with J_eff[c] += cc;
+ * node magnitudes, check rows, the stopping rule (pgw_pf_od's) and the outputs
+ * read J_eff.  Every env is solved.
+ * elem: c, the one element with elem_ctrl == 0 (n_ctrl = 1); not read with
+ * n_ctrl = 0 (no controllable load: K = 0).  wc: W_h[:, c], m complex (re, im). */
+typedef struct pgw_pf_h1 {
+  int32_t elem;
+  int32_t pad_;
+  double wc[2 * PGW_PF_MAX_M];
+} pgw_pf_h1;
+/* pgw_pf_solve's arguments and outputs, plus h (HOST pointer).  PGW_ERR_ARG,
+ * before any launch, for: t->od NULL; a shape other than m = 14 with one
+ * voltage band; n_ctrl > 1; n_ctrl = 1 with more or fewer than one element on
+ * slot 0 or h->elem not that element; U_init; load_scale; od resp / resp_v /
+ * resp_q. */
+int32_t pgw_pf_solve_h1(const pgw_pf_params* p, const pgw_pf_tables* t, const pgw_pf_h1* h, int64_t n,
+                        const double* ctrl_p, const double* ctrl_q, double* v_out, int32_t* iters,
+                        void* stream);
+/* fp32-storage variant, as pgw_pf_solve_f32. */
+int32_t pgw_pf_solve_h1_f32(const pgw_pf_params* p, const pgw_pf_tables* t, const pgw_pf_h1* h, int64_t n,
+                            const float* ctrl_p, const float* ctrl_q, float* v_out, int32_t* iters,
+                            void* stream);
+
 /* Response-table builder (OpenDSSSolver._od_response): the snap solve of
  * pgw_pf_od at n lanes, lane e at controllable kW P[e] (Q = 0) in hour
  * e / lanes_per_hour (a multiple of 256): hour h uses p_hours[h] (its base

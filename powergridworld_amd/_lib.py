@@ -114,6 +114,11 @@ class PFOD(C.Structure):
                 ("resp_q", vp), ("resp_q_rows", u64), ("resp_q_stride", i32), ("resp_q_k", i32)]
 
 
+class PFH1(C.Structure):
+    """pgw_pf_h1 (pgw_pf_solve_h1).  Not in STRUCTS: libpgw static_asserts its layout."""
+    _fields_ = [("elem", i32), ("pad_", i32), ("wc", f64 * (2 * PF_MAX_M))]
+
+
 OD_REC_HEAD = 6
 OD_VREC = 12                     # doubles per node record (PGW_OD_VREC)
 
@@ -356,6 +361,8 @@ _SIGS = {
     "pgw_agent_reduce": (i32, [P(ReduceArgs), i64, vp, vp, vp]),
     "pgw_pf_solve": (i32, [P(PFParams), P(PFTables), i64, vp, vp, vp, vp, vp]),
     "pgw_pf_solve_f32": (i32, [P(PFParams), P(PFTables), i64, vp, vp, vp, vp, vp]),
+    "pgw_pf_solve_h1": (i32, [P(PFParams), P(PFTables), P(PFH1), i64, vp, vp, vp, vp, vp]),
+    "pgw_pf_solve_h1_f32": (i32, [P(PFParams), P(PFTables), P(PFH1), i64, vp, vp, vp, vp, vp]),
     "pgw_pf_solve_general": (i32, [P(PFGParams), P(PFGTables), i64, vp, vp, vp, vp, vp]),
     "pgw_reg_factor": (i32, [P(RegParams), i64, vp, vp, vp, vp]),
     "pgw_reg_control": (i32, [P(RegParams), i64, vp, vp, vp, vp, vp, vp]),

@@ -116,6 +116,7 @@ template <int M, bool UB, bool GC> struct PFSolver {
   double pc, qc;           // slot-0 controllable kW / kvar of the env
   double lo2, mn2, mx2, tol2;
   static constexpr bool kMulti = false;   // (od_solve: see PFSolverMS)
+  static constexpr bool kH1 = false;      // (od_solve: see PFSolverH1)
 
   __device__ __forceinline__ void load(const PFArgs& a, const double* block) {
     const int l = threadIdx.x & 15;
@@ -1252,7 +1253,9 @@ template <int M> struct ODStage {
   double y0r, y0i, esc;                            // od_solve's resident element constants
 };
 
-template <int M>
+// ST = false (k_pf_solve_od_h1, which has no first-iteration table): the check
+// rows and the element constants only.
+template <int M, bool ST = true>
 __device__ __forceinline__ void od_stage_load(const ODArgs& o, const double* start, ODStage<M>& g) {
   constexpr int S = ODRow<M>::kStride;
   const int total = o.n_rows * S;
@@ -1269,10 +1272,12 @@ __device__ __forceinline__ void od_stage_load(const ODArgs& o, const double* sta
                              : o.rows_G + (2 * M * rc + (jc < 2 + M ? 2 * (jc - 2) : 2 * (jc - 2 - M) + 1));
     g.v[q] = has ? *p : 0.0;
   }
+  if constexpr (ST) {
 #pragma unroll
-  for (int q = 0; q < ODStage<M>::kStQ; ++q) {
-    const int i = threadIdx.x + q * kBlock;
-    g.v[ODStage<M>::kRowQ + q] = i < 12 * M ? start[i] : 0.0;
+    for (int q = 0; q < ODStage<M>::kStQ; ++q) {
+      const int i = threadIdx.x + q * kBlock;
+      g.v[ODStage<M>::kRowQ + q] = i < 12 * M ? start[i] : 0.0;
+    }
   }
   const int l = threadIdx.x & 15;
   const bool in = l < M;
@@ -1281,7 +1286,7 @@ __device__ __forceinline__ void od_stage_load(const ODArgs& o, const double* sta
   g.esc = in ? o.esc[l] : 0.0;
 }
 
-template <int M>
+template <int M, bool ST = true>
 __device__ __forceinline__ void od_stage_store(const ODArgs& o, const ODStage<M>& g, ODShared<M>& sh) {
   constexpr int S = ODRow<M>::kStride;
   const int total = o.n_rows * S;
@@ -1290,10 +1295,12 @@ __device__ __forceinline__ void od_stage_store(const ODArgs& o, const ODStage<M>
     const int i = threadIdx.x + q * kBlock;
     if (i < total) sh.rows[i] = g.v[q];
   }
+  if constexpr (ST) {
 #pragma unroll
-  for (int q = 0; q < ODStage<M>::kStQ; ++q) {
-    const int i = threadIdx.x + q * kBlock;
-    if (i < 12 * M) sh.st[i] = g.v[ODStage<M>::kRowQ + q];
+    for (int q = 0; q < ODStage<M>::kStQ; ++q) {
+      const int i = threadIdx.x + q * kBlock;
+      if (i < 12 * M) sh.st[i] = g.v[ODStage<M>::kRowQ + q];
+    }
   }
 }
 
@@ -1476,6 +1483,10 @@ constexpr uint64_t kFnvBasis = 0xcbf29ce484222325ull, kFnvPrime = 0x100000001b3u
 // PFSolverMS<M> (several: k_pf_solve_od_ms), whose caller has run iteration 1
 // (od_first_ms: u_1 in S, J_1 in sh.J[1]) and whose current law reads the
 // lane's own element powers; everything from iteration 2 on is the same code.
+// PFSolverH1<M> (k_pf_solve_od_h1, yprim="step") likewise runs iteration 1 itself
+// (od_first_h1); its current law takes y0' = the lane's own s_k, and its
+// correct() adds the env's rank-1 Yeq correction to the matvec's result and to
+// the stored currents -- compile-time branches on SV::kH1 only.
 template <int M, bool SIG = false, class SV = PFSolver<M, true, false>>
 __device__ int od_solve(SV& S, const ODArgs& o, const ODStage<M>& g, bool valid,
                         ODShared<M>& sh, uint64_t* sig = nullptr) {
@@ -1560,6 +1571,9 @@ __device__ int od_solve(SV& S, const ODArgs& o, const ODStage<M>& g, bool valid,
       nr[i] = A[i] - Bs[i];
       ni[i] = (C[i] - A[i]) - Bs[i];
     }
+    // yprim="step": the env's own Yeq change on the controllable element, between
+    // the matvec and the node tests; the stored currents become J_eff
+    if constexpr (SV::kH1) S.correct(nr, ni, !done, cur + tid);
     // ---- the square-root-free lower bound over the element nodes
     bool hit = false;
     static_for<0, M>([&](auto kk) {
@@ -3115,6 +3129,186 @@ __global__ void __launch_bounds__(kBlock) k_pf_solve_od_ms(PFArgs a, ODArgs o, p
   if (iters) iters[e] = it;
 }
 
+// ---- yprim = "step" (H1): every solve's Y holds its own loads' Yeq ----------
+// (pgw_pf_solve_h1, include/pgw.h.)  The block, the output rows and the check
+// rows are the hour's reduction (W_h, u0_h: Y with the hour's base-load Yeq);
+// the env's controllable power d = conj(S_ctrl) per phase sits on ONE element c,
+// so its Yeq change is a rank-1 update of Y and the correction one complex
+// scalar per env and solve, K = d / (1 - d W_h[c,c]).  Per iteration from u:
+//   J'_k = (s_k g_k - s_k) u_k        the compensation current with y0' = the
+//                                     step's own power s_k (k_pf_general's
+//                                     step_yeq), g current_od's band law;
+//   raw  = u0_h + W_h J'              the resident DPP matvec;
+//   cc   = K raw[c];  u_new = raw + W_h[:, c] cc;  J_eff = J', J_eff[c] += cc.
+// Every row V0_h + G_h J is affine in J_eff, which is what sh.J holds: the check
+// rows, the outputs and node 0 read it unchanged.  W_h[:, c], c and nph[c] are
+// uniform (kernel arguments: scalar registers); the lane keeps K and its (P, Q).
+struct H1Args {
+  double wcr[PGW_PF_MAX_M], wci[PGW_PF_MAX_M];   // W_h[:, c]
+  double wccr, wcci;                             // W_h[c, c]
+  double nph;                                    // phases of element c's load
+  int32_t c;                                     // the controllable element; -1: none (K = 0)
+};
+
+template <int M> struct PFSolverH1 : PFSolver<M, true, false> {
+  static constexpr bool kMulti = true;           // the caller runs iteration 1 (od_first_h1)
+  static constexpr bool kH1 = true;
+  double kr, ki;                                 // K of the env
+  double wcr[M], wci[M];                         // (uniform)
+  int c;                                         // (uniform)
+
+  // pc / qc set; K = d / (1 - d Wcc), d = (P 1000 / nph, -(Q 1000 / nph)); no
+  // controllable element: d = 0, K = 0
+  __device__ __forceinline__ void set_h1(const H1Args& h) {
+    c = h.c;
+#pragma unroll
+    for (int k = 0; k < M; ++k) {
+      wcr[k] = h.wcr[k];
+      wci[k] = h.wci[k];
+    }
+    const bool on = h.c >= 0;
+    const double dr = on ? (this->pc * 1000.0) / h.nph : 0.0;
+    const double di = on ? -((this->qc * 1000.0) / h.nph) : 0.0;
+    const double er = 1.0 - fma(dr, h.wccr, -(di * h.wcci));
+    const double ei = -fma(dr, h.wcci, di * h.wccr);
+    const double inv = 1.0 / fma(er, er, ei * ei);
+    kr = fma(dr, er, di * ei) * inv;               // d conj(e) / |e|^2
+    ki = fma(di, er, -(dr * ei)) * inv;
+  }
+
+  // PFSolver::current_od with y0' = the lane's own s_k (y0r / y0i unused)
+  template <int K>
+  __device__ __forceinline__ void current_od(double, double, double& ir, double& ii) const {
+    double s_r, s_i;
+    pf_power<M, K>(s_r, s_i, this->sres, this->pc, this->qc);
+    const double m2 = fma(this->ui[K], this->ui[K], this->ur[K] * this->ur[K]);
+    double mc = fmin(fmax(m2, this->mn2), this->mx2);
+    mc = (m2 <= this->lo2) ? 1.0 : mc;
+    const double g = fast_rcp(mc);
+    const double cr = fma(s_r, g, -s_r), ci = fma(s_i, g, -s_i);
+    ir = fma(cr, this->ur[K], -(ci * this->ui[K]));
+    ii = fma(cr, this->ui[K], ci * this->ur[K]);
+  }
+
+  // (xr, xi) = the matvec's result: cc = K x[c], x += W_h[:, c] cc; with `store`
+  // the lane's stored current of element c (jc: its slot of element 0) gets cc
+  __device__ __forceinline__ void correct(double (&xr)[M], double (&xi)[M], bool store, double2* jc) const {
+    double ar = 0.0, ai = 0.0;
+#pragma unroll
+    for (int k = 0; k < M; ++k) {
+      ar = (c == k) ? xr[k] : ar;                  // (uniform select)
+      ai = (c == k) ? xi[k] : ai;
+    }
+    const double ccr = fma(kr, ar, -(ki * ai)), cci = fma(kr, ai, ki * ar);
+#pragma unroll
+    for (int i = 0; i < M; ++i) {
+      xr[i] = fma(wcr[i], ccr, fma(-wci[i], cci, xr[i]));
+      xi[i] = fma(wcr[i], cci, fma(wci[i], ccr, xi[i]));
+    }
+    if (store && c >= 0) {
+      double2 j = jc[c * kBlock];
+      j.x += ccr;
+      j.y += cci;
+      jc[c * kBlock] = j;
+    }
+  }
+};
+
+// Iteration 1 (block and powers loaded, K set): the start is the direct
+// solution at the env's own Y, u_start = u0_h + W_h[:, c] K u0_h[c] -- not
+// affine in (P, Q), so a full iteration from it: u_1 into S, J_eff_1 into the
+// lane's sh.J[1] slots, where iteration 2 expects the previous currents (and
+// the outputs' input when max_iter = 1).
+template <int M>
+__device__ __forceinline__ void od_first_h1(PFSolverH1<M>& S, ODShared<M>& sh) {
+  const int tid = threadIdx.x;
+  pf_u0<M>(S.ur, S.ui, S.w);
+  S.correct(S.ur, S.ui, false, nullptr);
+  double A[M], Bs[M], C[M];
+  pf_acc_init<M>(A, C, S.w);
+#pragma unroll
+  for (int i = 0; i < M; ++i) Bs[i] = 0.0;
+  static_for<0, M>([&](auto kk) {
+    constexpr int k = decltype(kk)::value;
+    double ir, ii;
+    S.template current_od<k>(0.0, 0.0, ir, ii);
+    pf_column<M, k>(A, Bs, C, S.w, ir, ii, ir + ii);
+    sh.J[1][k * kBlock + tid] = make_double2(ir, ii);
+  });
+#pragma unroll
+  for (int i = 0; i < M; ++i) {
+    S.ur[i] = A[i] - Bs[i];
+    S.ui[i] = (C[i] - A[i]) - Bs[i];
+  }
+  S.correct(S.ur, S.ui, true, sh.J[1] + tid);
+}
+
+// pgw_pf_solve_h1: k_pf_solve_od_ms's shape -- no response table, every env is
+// solved, the output rows' loads issued after the solve.
+template <int M, class IO = double>
+__global__ void __launch_bounds__(kBlock) k_pf_solve_od_h1(PFArgs a, ODArgs o, H1Args h, pgw_pf_tables t,
+                                                           int64_t n, const IO* __restrict__ ctrl_p,
+                                                           const IO* __restrict__ ctrl_q,
+                                                           IO* __restrict__ v_out,
+                                                           int32_t* __restrict__ iters) {
+  const int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  const bool valid = e < n;
+  __shared__ ODShared<M> sh;
+  ODStage<M> stg;
+  const bool rows_lds = od_rows_lds<M>(a.n_out);     // (uniform)
+  PFSolverH1<M> S;
+  od_stage_load<M, false>(o, nullptr, stg);
+  S.load(a, t.block);
+  S.pc = (valid && a.n_ctrl > 0 && ctrl_p) ? (double)ctrl_p[e] : 0.0;
+  S.qc = (valid && a.n_ctrl > 0 && ctrl_q) ? (double)ctrl_q[e] : 0.0;
+  S.set_h1(h);
+  od_stage_store<M, false>(o, stg, sh);
+  od_first_h1<M>(S, sh);                             // (reads no staged LDS)
+  __syncthreads();                                   // the staged check rows
+  int it = 0;
+  if (__ballot(valid) != 0ull)                       // (wave-uniform) some env of this wave
+    it = od_solve<M, false, PFSolverH1<M>>(S, o, stg, valid, sh);
+  double rv[kOdRowQ];
+  if (rows_lds) od_rows_issue<M>(t, a.n_out, rv);
+  double ir[M], ii[M], v0r = 0.0, v0i = 0.0;
+  od_load_J<M>(sh, it, ir, ii);
+  pf_node0<M>(v0r, v0i, S.w, ir, ii);
+  const double m2_0 = fma(v0i, v0i, v0r * v0r);
+  const double v0 = sqrt(m2_0);
+  if (valid && t.U_out) {
+#pragma unroll
+    for (int k = 0; k < M; ++k) {
+      t.U_out[2 * (e * M + k)] = S.ur[k];
+      t.U_out[2 * (e * M + k) + 1] = S.ui[k];
+    }
+  }
+  double vmn = v0, vmx = v0;      // Python min()/max() over the rows in order
+  const double* srow = rows_lds ? od_rows_put<M>(sh, a.n_out, rv) : nullptr;
+  if (v_out || !rows_lds) {
+    pf_rows_out<M>(t, rows_lds, srow, a.n_out, ir, ii, [&](int ro, double v) {
+      if (valid && v_out) v_out[(int64_t)ro * n + e] = (IO)v;
+      vmn = (v < vmn) ? v : vmn;
+      vmx = (v > vmx) ? v : vmx;
+    });
+  } else {
+    // extrema only (as k_pf_solve_od)
+    double mn2 = m2_0, mx2 = mn2;
+    pf_rows_out<M, false>(t, rows_lds, srow, a.n_out, ir, ii, [&](int, double m2) {
+      mn2 = (m2 < mn2) ? m2 : mn2;
+      mx2 = (m2 > mx2) ? m2 : mx2;
+    });
+    vmn = sqrt(mn2);
+    vmx = sqrt(mx2);
+  }
+  if (!valid) return;
+  if (a.n_out > 0) {
+    if (v_out) v_out[e] = (IO)v0;
+    if (t.v_min_out) t.v_min_out[e] = vmn;
+    if (t.v_max_out) t.v_max_out[e] = vmx;
+  }
+  if (iters) iters[e] = it;
+}
+
 // Response-table builder (pgw_pf_od_probe): the snap solve at lane e's kW P[e]
 // (Q = 0) in hour e / lanes_per_hour -- that hour's PFArgs (base loads) and
 // first-iteration table -- with the signature of its pieces.
@@ -3941,7 +4135,64 @@ static int32_t pf_solve(const pgw_pf_params* p, const pgw_pf_tables* t, int64_t 
   PGW_PF_DISPATCH(*p, *t, launch_pf_solve, a, *t, n, ctrl_p, ctrl_q, v_out, iters, (hipStream_t)stream);
 }
 
+// pgw_pf_solve_h1 / pgw_pf_solve_h1_f32
+static_assert(sizeof(pgw_pf_h1) == 8 + 16 * PGW_PF_MAX_M && offsetof(pgw_pf_h1, wc) == 8, "pgw_pf_h1 layout");
+template <class IO>
+static int32_t pf_solve_h1(const pgw_pf_params* p, const pgw_pf_tables* t, const pgw_pf_h1* h, int64_t n,
+                           const IO* ctrl_p, const IO* ctrl_q, IO* v_out, int32_t* iters, void* stream) {
+  PGW_REQUIRE(p && t && h && t->block && n >= 0, "pgw_pf_solve_h1: null argument");
+  PGW_REQUIRE(t->od, "pgw_pf_solve_h1: tables without od (the OpenDSS rule's check rows)");
+  const pgw_pf_od* d = t->od;
+  PGW_REQUIRE(p->m == 14 && uniform_band(*p), "pgw_pf_solve_h1: needs the fast shape, m = 14 and one voltage band "
+              "(use pgw_pf_solve_general with PGW_PF_OPENDSS_STEP)");
+  PGW_REQUIRE(p->n_ctrl >= 0 && p->n_ctrl <= 1, "pgw_pf_solve_h1: %d controllable slots (at most one)", p->n_ctrl);
+  PGW_REQUIRE(!t->U_init && !t->load_scale, "pgw_pf_solve_h1: takes no U_init / load_scale");
+  PGW_REQUIRE(!d->resp && !d->resp_v && !d->resp_q,
+              "pgw_pf_solve_h1: takes no response table (od resp / resp_v / resp_q must be NULL)");
+  int on0 = 0;
+  for (int k = 0; k < p->m; ++k) on0 += p->elem_ctrl[k] == 0;
+  PGW_REQUIRE(p->n_ctrl == 0 || (on0 == 1 && h->elem >= 0 && h->elem < p->m && p->elem_ctrl[h->elem] == 0),
+              "pgw_pf_solve_h1: slot 0 must hold exactly one element, pgw_pf_h1.elem (%d elements, elem %d)", on0,
+              h->elem);
+  PGW_REQUIRE(p->n_out == 0 || (t->G && t->V0), "pgw_pf_solve_h1: missing G/V0");
+  PGW_REQUIRE(p->n_out == 0 || v_out || t->v_min_out || t->v_max_out,
+              "pgw_pf_solve_h1: n_out > 0 but no output (v_out, v_min_out, v_max_out all NULL)");
+  PGW_REQUIRE(d->n_rows >= 0 && d->n_rows <= PGW_PF_OD_MAX_ROWS && d->n_rep >= 0 && d->n_rep <= d->n_rows,
+              "pgw_pf_solve_h1: od n_rep %d / n_rows %d (<= %d)", d->n_rep, d->n_rows, PGW_PF_OD_MAX_ROWS);
+  // (the stage's loads issue unconditionally: one dummy row when n_rows = 0)
+  PGW_REQUIRE(d->rows_V0 && d->rows_G, "pgw_pf_solve_h1: od rows missing");
+  PGW_REQUIRE(d->min_iter >= 2 && p->max_iter >= 1 && d->tol >= 0.0, "pgw_pf_solve_h1: od min_iter / max_iter / tol");
+  if (n == 0) return PGW_OK;
+  H1Args ha = {};
+  ha.c = p->n_ctrl == 1 ? h->elem : -1;
+  ha.nph = 1.0;
+  if (ha.c >= 0) {
+    for (int k = 0; k < p->m; ++k) {
+      ha.wcr[k] = h->wc[2 * k];
+      ha.wci[k] = h->wc[2 * k + 1];
+    }
+    ha.wccr = ha.wcr[ha.c];
+    ha.wcci = ha.wci[ha.c];
+    ha.nph = p->nph[ha.c];
+  }
+  launch_timed(PGW_T_PF_SOLVE, k_pf_solve_od_h1<14, IO>, dim3(grid_for(n)), dim3(kBlock), (hipStream_t)stream,
+               make_pf_args(*p, *t), make_od_args(*d, p->max_iter), ha, *t, n, ctrl_p, ctrl_q, v_out, iters);
+  return check_launch("k_pf_solve_od_h1");
+}
+
 extern "C" {
+
+int32_t pgw_pf_solve_h1(const pgw_pf_params* p, const pgw_pf_tables* t, const pgw_pf_h1* h, int64_t n,
+                        const double* ctrl_p, const double* ctrl_q, double* v_out, int32_t* iters,
+                        void* stream) {
+  return pf_solve_h1(p, t, h, n, ctrl_p, ctrl_q, v_out, iters, stream);
+}
+
+int32_t pgw_pf_solve_h1_f32(const pgw_pf_params* p, const pgw_pf_tables* t, const pgw_pf_h1* h, int64_t n,
+                            const float* ctrl_p, const float* ctrl_q, float* v_out, int32_t* iters,
+                            void* stream) {
+  return pf_solve_h1(p, t, h, n, ctrl_p, ctrl_q, v_out, iters, stream);
+}
 
 int32_t pgw_pf_solve(const pgw_pf_params* p, const pgw_pf_tables* t, int64_t n,
                      const double* ctrl_p, const double* ctrl_q, double* v_out, int32_t* iters,

@@ -132,6 +132,44 @@ def od_start_table(W2, u0, y0, base_kw, base_kvar, nph, affine):
     return np.concatenate(parts).view(np.float64)
 
 
+def h1_yeq_change(base_kw, base_kvar, nph, y0):
+    """yprim="step": the hour's base-load Yeq change dD [M] against the DSS
+    file's (per element, W - j var per phase): the kernel's own per-phase power
+    of the hour (base_kw / base_kvar [M]: the hour's loads per element) less
+    y0 [M] complex, the Yeq powers in the file model's Y.  Pure NumPy."""
+    nph = np.asarray(nph, float)
+    s = (np.asarray(base_kw, float) * 1000.0) / nph - 1j * ((np.asarray(base_kvar, float) * 1000.0) / nph)
+    return s - np.asarray(y0, complex)
+
+
+def h1_hour_reduction(W2, u0, dD):
+    """The hour's reduction from the file model's (W2 [M, M], u0 [M], pu): u =
+    u0 + W J with J = J' + dD u gives W_h = (I - W dD)^-1 W (complex symmetric,
+    symmetrised against rounding) and u0_h = (I - W dD)^-1 u0.  Pure NumPy."""
+    A = np.eye(len(u0)) - W2 * dD[None, :]
+    Wh = np.linalg.solve(A, W2)
+    return 0.5 * (Wh + Wh.T), np.linalg.solve(A, u0)
+
+
+def h1_hour_rows(G, V0, dD, Wh, u0h):
+    """Rows V0 + G J of the file model (G [R, M], V0 [R]) as the hour's V0_h +
+    G_h J': G_h = G (I + dD W_h), V0_h = V0 + G dD u0_h.  Pure NumPy."""
+    GD = G * dD[None, :]
+    return G + GD @ Wh, V0 + GD @ u0h
+
+
+def h1_hour_tables(W2, u0, y0, base_kw, base_kvar, nph, G_out, V0_out, G_chk, V0_chk, elem):
+    """Everything pgw_pf_solve_h1 reads of one hour (include/pgw.h, pgw_pf_h1):
+    dict(W, u0: the block's operands; G, V0: the output rows; Gc, V0c: the check
+    rows; wc: W_h[:, elem] [M] complex, zeros with elem < 0).  Pure NumPy."""
+    dD = h1_yeq_change(base_kw, base_kvar, nph, y0)
+    Wh, u0h = h1_hour_reduction(W2, u0, dD)
+    G, V0 = h1_hour_rows(G_out, V0_out, dD, Wh, u0h)
+    Gc, V0c = h1_hour_rows(G_chk, V0_chk, dD, Wh, u0h)
+    wc = Wh[:, elem].copy() if elem >= 0 else np.zeros(len(u0), complex)
+    return dict(W=Wh, u0=u0h, G=G, V0=V0, Gc=Gc, V0c=V0c, wc=wc)
+
+
 class OpenDSSSolver(PowerFlowSolver):
 
     # Per-hour predictor grid (single controllable load): the batched solve
@@ -152,7 +190,7 @@ class OpenDSSSolver(PowerFlowSolver):
                  output_nodes=None, predictor: bool = True, warm_start: bool = False,
                  convergence: str = "opendss", general: bool = None, od_table: bool = True,
                  snap_start: str = "direct", yprim: str = "dss_file", control_loop: str = "host",
-                 multi_bus: str = "general", **kwargs):
+                 multi_bus: str = "general", step_kernel: str = "general", **kwargs):
         """convergence: "opendss" (the default) -- OpenDSS's own snap solve as
         the reference runs it (opendss.py:134):
         loads' nominal admittances in Y, start from the direct solution, stop at
@@ -195,8 +233,21 @@ class OpenDSSSolver(PowerFlowSolver):
         multi-slot instantiation (k_pf_solve_od_ms: per-lane element powers,
         the closed-form first iteration over every slot, no response table --
         od_table is ignored there, every env is solved), which the fused
-        multi-agent step then runs too; `general` / `_od_fast` tell which."""
+        multi-agent step then runs too; `general` / `_od_fast` tell which.
+        step_kernel (yprim="step"; nothing changes otherwise): "general" (the
+        default) -- the general kernel as described above; "fast" -- on a
+        feeder of the fast shape with at most one controllable load of one
+        phase element, the fast one-lane-per-env kernel (pgw_pf_solve_h1,
+        k_pf_solve_od_h1): the hour's reduction packed per hour and cached on
+        the device, the env's correction K formed in the kernel -- no per-step
+        torch arithmetic --, and the fused multi-agent step runs it too.
+        Anything else (a delta load such as 671, several controllable loads,
+        other feeders) falls back to the general kernel; `general` tells which
+        route runs."""
         super().__init__(**kwargs)
+        if step_kernel not in ("general", "fast"):
+            raise ValueError("step_kernel must be 'general' or 'fast', got %r" % (step_kernel,))
+        self.step_kernel = step_kernel
         if multi_bus not in ("general", "fast"):
             raise ValueError("multi_bus must be 'general' or 'fast', got %r" % (multi_bus,))
         self.multi_bus = multi_bus
@@ -220,7 +271,9 @@ class OpenDSSSolver(PowerFlowSolver):
                              "(convergence='opendss', snap_start='direct')")
         self.yprim = yprim
         if yprim == "step":
-            general, od_table = True, False
+            od_table = False
+            if step_kernel != "fast":
+                general = True
         self.convergence = convergence
         self.od_table = bool(od_table)
         self.num_envs = int(num_envs)
@@ -243,6 +296,9 @@ class OpenDSSSolver(PowerFlowSolver):
                          len({(a, b, c) for a, b, c in zip(f.elem_vmin, f.elem_vmax, f.elem_vlow)}) == 1)
         self.general = (bool(general) or (convergence == "opendss" and not self._od_fast)
                         or f.m > _lib.PF_MAX_M or not model1 or regctl)
+        # yprim="step" on the fast kernel (step_kernel="fast"; pgw_pf_solve_h1)
+        self._h1_fast = yprim == "step" and self._od_fast
+        self._h1f_cache = {}
         if self.feeder.m > _lib.PFG_MAX_M:
             raise ValueError("feeder has %d load phase elements (max %d)" % (self.feeder.m, _lib.PFG_MAX_M))
         if convergence == "opendss":
@@ -309,6 +365,7 @@ class OpenDSSSolver(PowerFlowSolver):
         self.output_names = names
         self._names_ver = getattr(self, "_names_ver", 0) + 1
         idx = [f.node_index[n] for n in names]
+        self._out_idx = idx
         if self.general:
             return self._set_general_tables(idx)
         # OpenDSS rule: the reduction of its iteration matrix (Y + the loads' Yeq;
@@ -416,6 +473,7 @@ class OpenDSSSolver(PowerFlowSolver):
         cdev = lambda a: torch.tensor(np.ascontiguousarray(a).view(np.float64).ravel(), dtype=torch.float64,
                                       device=dev)
         self._od_Gall, self._od_V0all = Gs, V0s          # every node's row (the node records)
+        self._od_row_idx = rows
         self._od_rows_V0 = cdev(V0s[rows] if rows else np.zeros(1, complex))
         self._od_rows_G = cdev(Gs[rows] if rows else np.zeros((1, M), complex))
         od.rows_V0, od.rows_G = self._od_rows_V0.data_ptr(), self._od_rows_G.data_ptr()
@@ -1178,7 +1236,12 @@ class OpenDSSSolver(PowerFlowSolver):
         if names != self._ctrl_names:
             self._ctrl_names = names
             self._seen_keys = None
-            if self._od_fast and len(names) > 1 and self.multi_bus != "fast":
+            if self._h1_fast and not self.h1_fast_serves(names):
+                # yprim="step": the fast kernel takes one controllable load of
+                # one phase element; anything else runs the general kernel
+                self._od_fast, self.general, self._h1_fast = False, True, False
+                self.set_output_nodes(self.output_names)
+            elif self._od_fast and not self._h1_fast and len(names) > 1 and self.multi_bus != "fast":
                 # several controllable slots run the general kernel unless
                 # multi_bus="fast" asks for the fast kernel's multi-slot
                 # instantiation (k_pf_solve_od_ms: no response table)
@@ -1186,6 +1249,68 @@ class OpenDSSSolver(PowerFlowSolver):
                 self.set_output_nodes(self.output_names)
             else:
                 self._base_params()
+
+    def h1_fast_serves(self, names):
+        """yprim="step", step_kernel="fast": whether the fast kernel serves these
+        controllable loads -- none, or one load of one phase element."""
+        f = self.feeder
+        names = [n for n in names if n in self.load_bus_name]
+        elems = [k for k in range(f.m) if f.load_names[f.elem_load[k]] in names]
+        return self._h1_fast and len(names) <= 1 and len(elems) == len(names)
+
+    def _h1f_tables(self, hour):
+        """yprim="step" on the fast kernel: the hour's PFTables -- the packed
+        block of (W_h, u0_h) with output row 0, the output rows, every check row
+        (n_rep = n_rows: the bound constants hold for the file model's rows, not
+        the hour's) -- with pgw_pf_h1 (the controllable element, W_h[:, c]) as
+        its `_h1`.  One upload per (hour, configuration), cached on the device."""
+        key = (hour, self._cfg_version)
+        t = self._h1f_cache.get(key)
+        if t is not None:
+            return t
+        M, od0, p = self.M, self._od_proto, self._params_for_hour(hour)
+        ctrl = [k for k in range(M) if p.elem_ctrl[k] == 0]
+        elem = ctrl[0] if len(ctrl) == 1 and p.n_ctrl == 1 else -1
+        rows = self._od_row_idx
+        y0 = np.array(od0.y0r[:M]) + 1j * np.array(od0.y0i[:M])
+        c = h1_hour_tables(self._od_W2, self._od_u0, y0, np.array(p.base_kw[:M]), np.array(p.base_kvar[:M]),
+                           np.array(p.nph[:M]), self._od_Gall[self._out_idx], self._od_V0all[self._out_idx],
+                           self._od_Gall[rows] if rows else np.zeros((1, M), complex),
+                           self._od_V0all[rows] if rows else np.zeros(1, complex), elem)
+        vb = np.array(p.vbase[:M])
+        flat = lambda a: np.ascontiguousarray(a, dtype=complex).view(np.float64).ravel()
+        block = np.zeros(int(_lib.lib().pgw_pf_pack_size(M)))
+        cp = lambda a: a.ctypes.data_as(_lib.C.c_void_p)
+        no = len(self._out_idx)
+        G0 = flat(c["G"][0]) if no else np.zeros(2 * M)
+        V00 = flat(c["V0"][:1]) if no else np.zeros(2)
+        # (pgw_pf_pack divides by the element bases: hand it volts)
+        Wv, U0v = flat(c["W"] * (vb[:, None] * vb[None, :])), flat(c["u0"] * vb)
+        _lib.check(_lib.lib().pgw_pf_pack(p, cp(Wv), cp(U0v), cp(G0), cp(V00), cp(block)))
+        parts = [block, flat(c["G"]) if no else np.zeros(2 * M), flat(c["V0"]) if no else np.zeros(2),
+                 flat(c["V0c"]), flat(c["Gc"])]
+        offs = np.cumsum([0] + [len(a) for a in parts])
+        buf = torch.tensor(np.concatenate(parts), dtype=torch.float64, device=self.device)
+        at = lambda i: buf.data_ptr() + 8 * int(offs[i])
+        od = _lib.PFOD.from_buffer_copy(od0)
+        od.rows_V0, od.rows_G, od.start = at(3), at(4), None
+        od.n_rep = od.n_rows                       # every check row evaluated
+        od.resp = od.resp_v = od.resp_q = None
+        od.resp_v_row = -1
+        t = _lib.PFTables.from_buffer_copy(self.tables)
+        t.block, t.G, t.V0 = at(0), at(1), at(2)
+        t.od = _lib.C.addressof(od)
+        h = _lib.PFH1()
+        h.elem = elem
+        wc = flat(c["wc"])
+        for i in range(2 * M):
+            h.wc[i] = wc[i]
+        t._h1, t._keep = h, (od, buf)              # (they live as long as these tables)
+        if len(self._h1f_cache) > 64:
+            self._h1f_cache.clear()
+            self.tables_version += 1
+        self._h1f_cache[key] = t
+        return t
 
     def _base_params(self):
         if self.general:
@@ -1300,6 +1425,8 @@ class OpenDSSSolver(PowerFlowSolver):
         PREDICTOR_LOOKAHEAD - 1 hours in ONE launch (the hours differ only by
         the loadshape coefficient, passed as a per-env load scale), so an
         episode pays for about one table solve.  Otherwise the cold-start tables."""
+        if self._h1_fast:
+            return self._h1f_tables(self.hour_of(current_time))
         if self._od_fast:
             return self._od_tables(self.hour_of(current_time))
         if self.general or not (self.use_predictor and len(self._ctrl_names) == 1):
@@ -1406,11 +1533,15 @@ class OpenDSSSolver(PowerFlowSolver):
                 cp = torch.stack([x if x is not None else zeros for x in ps])
                 cq = torch.stack([x if x is not None else zeros for x in qs])
         tables = self.solve_tables(current_time, cp is not None)
-        if self.yprim == "step":
+        if self.yprim == "step" and not self._h1_fast:
             tables = self._h1_tables(self.hour_of(current_time), cp, cq)
         fn = _lib.lib().pgw_pf_solve_general if self.general else _lib.lib().pgw_pf_solve
         if self.regulators is not None:
             self._solve_regulated(fn, p, tables, cp, cq)
+        elif self._h1_fast:
+            _lib.check(_lib.lib().pgw_pf_solve_h1(p, tables, tables._h1, n, _lib.dptr(cp), _lib.dptr(cq),
+                                                  _lib.dptr(self.v_out), _lib.dptr(self._iters),
+                                                  _lib.stream_ptr(self.device)))
         else:
             _lib.check(fn(p, tables, n, _lib.dptr(cp), _lib.dptr(cq), _lib.dptr(self.v_out),
                           _lib.dptr(self._iters), _lib.stream_ptr(self.device)))

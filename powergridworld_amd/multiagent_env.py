@@ -696,8 +696,11 @@ class MultiAgentEnv(Env):
                 return "RegControl on the fused multi-agent step is fp64 only"
         if getattr(self.pf_solver, "snap_start", "direct") != "direct":
             return "snap_start='previous' (each env's solve starts from its own previous solution)"
-        if getattr(self.pf_solver, "yprim", "dss_file") != "dss_file":
-            return "yprim='step' (every solve's Y holds its own loads' admittances)"
+        if getattr(self.pf_solver, "yprim", "dss_file") != "dss_file" and \
+                not self.pf_solver.h1_fast_serves(sorted(set(self.agent_name_bus_map.values()))):
+            # step_kernel="fast" with the agents on one load of one phase element:
+            # pgw_ma_step's agents, then pgw_pf_solve_h1 on the bus loads
+            return "yprim='step' (every solve's Y holds its own loads' admittances) on the general kernel"
         if len(self.agents) > _lib.MAX_AGENTS:
             return "more than %d agents" % _lib.MAX_AGENTS
         cls = type(self)
@@ -812,6 +815,8 @@ class MultiAgentEnv(Env):
                     "lazy_v": _FusedVoltages(self, {}, 0), "bufv": self._ma_bufv(plan),
                     "gen": ComponentEnv._bufv_gen, "fn": _lib.lib().pgw_ma_step_f32 if f32 else _lib.lib().pgw_ma_step,
                     "general": _lib.lib().pgw_pf_solve_general if solver.general else None,
+                    # yprim="step" on the fast kernel: pgw_pf_solve_h1 after the agents' step
+                    "h1": _lib.lib().pgw_pf_solve_h1 if getattr(solver, "_h1_fast", False) else None,
                     # RegControls (control_loop="device"): the solver's own launch of
                     # pgw_pf_solve_regulated in place of the general power flow
                     "regloop": solver.regulators is not None}
@@ -856,6 +861,10 @@ class MultiAgentEnv(Env):
                 solver.bind_output(None)
             solver._solve_regulated(None, pfp, pft, M["bus_p"] if args.n_bus else None, None,
                                     v_out=H["v"][s_] if H is not None else solver.v_out, iters=M["iters"])
+        elif M["h1"] is not None:     # the agents' step, then the yprim="step" fast solve on its bus loads
+            rc = M["fn"](args, None, None, self.num_envs, None, None, st) or \
+                M["h1"](pfp, pft, pft._h1, self.num_envs, M["bus_p"].data_ptr() if args.n_bus else None, None,
+                        v_out, M["iters"].data_ptr(), st)
         elif M["general"] is None:
             rc = M["fn"](args, pfp, pft, self.num_envs, v_out, M["iters"].data_ptr(), st)
         else:     # the agents' step, then the general power flow on its bus loads

@@ -13,7 +13,10 @@ on the generic path, fused=False; HETF: HET with fp32 storage
 (pgw_ma_step_f32); HETMG / HETMF: the heterogeneous agents on three buses
 (675c, 634a, 684c), the power flow on the general kernel (multi_bus="general",
 the default route) / on the fast kernel's multi-slot instantiation
-(multi_bus="fast"); C3F / C3G8F:
+(multi_bus="fast"); HETYG / HETYF: the heterogeneous scenario under
+yprim="step" (every solve's Y holds its own loads' Yeq), the generic agents and
+the general kernel (step_kernel="general", the default) / the fused multi-agent
+step and the fast kernel (step_kernel="fast", pgw_pf_solve_h1); C3F / C3G8F:
 C3 with fp32 storage (pgw_mc_agent_step_f32); C3L: C3 at
 65 536 envs; C2Gk / C3Gk: the step replayed from captured hipGraphs of k steps,
 C3 through the device clocks; C3Pk / HSPk: captured once per episode position,
@@ -152,7 +155,7 @@ def bench_c3(dev, steps, warmup, n=16384, pool=16, graph=0, clocked=True, dtype=
 
 
 def bench_het(dev, steps, warmup, n=65536, pool=16, fused="auto", conv="opendss", table=True, vrec=True, qrec=True,
-              rrows=True, dtype=torch.float64, multi_bus=None):
+              rrows=True, dtype=torch.float64, multi_bus=None, step_kernel=None):
     from powergridworld_amd.scenarios.heterogeneous import make_env_config
     from powergridworld_amd.multiagent_env import MultiAgentEnv
     cfg = make_env_config(pf_convergence=conv)
@@ -160,6 +163,9 @@ def bench_het(dev, steps, warmup, n=65536, pool=16, fused="auto", conv="opendss"
         for a, bus in zip(cfg["agents"], MULTI_BUSES):
             a["bus"] = bus
         cfg["pf_config"]["config"]["multi_bus"] = multi_bus
+        table = False
+    if step_kernel:                # yprim="step": no response table, every env is solved
+        cfg["pf_config"]["config"].update(yprim="step", step_kernel=step_kernel)
         table = False
     env = MultiAgentEnv(**cfg, num_envs=n, device=dev, fused=fused, dtype=dtype)
     env.pf_solver.od_table = table
@@ -191,6 +197,8 @@ def bench_het(dev, steps, warmup, n=65536, pool=16, fused="auto", conv="opendss"
         + ("F" if dtype == torch.float32 else "")
     if multi_bus:
         name = "HETM" + multi_bus[0].upper()
+    if step_kernel:
+        name = "HETY" + step_kernel[0].upper()
     return dict(config=name,
                 workload="3-agent heterogeneous (MC building, grid-aware PV farm, EV 25x40)"
                          + (" on buses %s" % ", ".join(MULTI_BUSES) if multi_bus else "") + " + IEEE-13 PF, "
@@ -198,6 +206,7 @@ def bench_het(dev, steps, warmup, n=65536, pool=16, fused="auto", conv="opendss"
                             if env._ma is not None else "generic path"),
                 pf_convergence=conv, pf_response_table=bool(table and conv == "opendss"),
                 pf_kernel="general" if env.pf_solver.general else "fast",
+                pf_yprim=getattr(env.pf_solver, "yprim", "dss_file"),
                 batch=n, agents=3, steps=steps, seconds=dt)
 
 
@@ -255,6 +264,8 @@ def main():
            "HETF": lambda *a: bench_het(*a, dtype=torch.float32),
            "HETMG": lambda *a: bench_het(*a, multi_bus="general"),
            "HETMF": lambda *a: bench_het(*a, multi_bus="fast"),
+           "HETYG": lambda *a: bench_het(*a, step_kernel="general"),
+           "HETYF": lambda *a: bench_het(*a, step_kernel="fast"),
            "C2G1": lambda *a: bench_c2(*a, graph=1), "C2G8": lambda *a: bench_c2(*a, graph=8),
            "C3G1": lambda *a: bench_c3(*a, graph=1), "C3G8": lambda *a: bench_c3(*a, graph=8),
            "C3P1": lambda *a: bench_c3(*a, graph=1, clocked=False),

@@ -1,0 +1,129 @@
+"""Same-box A/B of OpenDSSSolver(yprim="step", step_kernel="general" | "fast")
+at 65,536 envs, one process, the two alternated in every round:
+  * the stand-alone power flow on 675c with every node written (the solver's
+    entry and per-step host work -- on the general route the torch chain that
+    forms K -- `reps` solves between two device events), after a check that
+    both give equal iteration counts and voltages within 1e-11 rel;
+  * the heterogeneous scenario's step (tools/bench_configs.py HETYG / HETYF:
+    the generic agents and the general kernel against the fused multi-agent
+    step and pgw_pf_solve_h1), host clock around synchronised regions;
+  * the C4 scenario's generic step (the one-launch step refuses yprim="step")
+    with the solve on either kernel.
+Usage: python tools/gpu/ab_h1.py [rounds] [reps] [steps]"""
+import os
+import sys
+import time
+
+import numpy as np
+import pandas as pd
+import torch
+
+TOOLS = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.dirname(TOOLS))      # the repository root: powergridworld_amd
+from powergridworld_amd.distribution_system.opendss import OpenDSSSolver   # noqa: E402
+from powergridworld_amd.multiagent_env import MultiAgentEnv   # noqa: E402
+
+dev = torch.device("cuda", 0)
+n = 65536
+rounds = int(sys.argv[1]) if len(sys.argv) > 1 else 4
+reps = int(sys.argv[2]) if len(sys.argv) > 2 else 200
+steps = int(sys.argv[3]) if len(sys.argv) > 3 else 286
+T = pd.Timestamp("08-12-2021 11:10:00")
+MODES = ("general", "fast")
+
+# ---------------------------------------------------------------- stand-alone power flow, every node
+rng = np.random.default_rng(1)
+P = rng.uniform(-400.0, 900.0, n)
+Q = rng.uniform(-0.3, 0.5, n) * np.abs(P)
+Pd, Qd = {"675c": torch.tensor(P, device=dev)}, {"675c": torch.tensor(Q, device=dev)}
+runs = {}
+for mode in MODES:
+    s = OpenDSSSolver("ieee_13_dss/IEEE13Nodeckt.dss", "ieee_13_dss/annual_hourly_load_profile.csv", device=dev,
+                      system_load_rescale_factor=1.2, convergence="opendss", num_envs=n, yprim="step",
+                      step_kernel=mode)
+    s.set_controllable_loads(["675c"])
+    assert s.general == (mode == "general") and s._h1_fast == (mode == "fast")
+    assert len(s.output_names) == s.feeder.n
+    call = (lambda s=s: s.calculate_power_flow(Pd, Qd, current_time=T))
+    for _ in range(20):
+        call()
+    torch.cuda.synchronize()
+    runs[mode] = (s, call)
+vg, vf = runs["general"][0].v_out, runs["fast"][0].v_out
+ig, if_ = runs["general"][0].iterations, runs["fast"][0].iterations
+print("PF: iterations equal %s, fast vs general %.3e rel, iteration histogram %s"
+      % (bool(torch.equal(ig, if_)), ((vf - vg).abs() / vg.abs()).max().item(),
+         torch.bincount(if_.clamp(min=0)).tolist()), flush=True)
+for r in range(rounds):
+    out = []
+    for mode in MODES:
+        call = runs[mode][1]
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        for _ in range(reps):
+            call()
+        e1.record()
+        torch.cuda.synchronize()
+        out.append(e0.elapsed_time(e1) / reps * 1e3)
+    print("PF round %d: general %.2f us/solve  fast %.2f us/solve  ratio %.3f" % (r, out[0], out[1], out[0] / out[1]),
+          flush=True)
+del runs
+
+
+# ---------------------------------------------------------------- env steps
+def actions(env, count=8):
+    gen = torch.Generator(dev).manual_seed(0)
+    draw = lambda d: torch.empty((n, d), dtype=torch.float64, device=dev).uniform_(-1, 1, generator=gen)
+    return [{ag.name: ({c.name: draw(c.action_space.shape[0]) for c in ag.envs} if hasattr(ag, "envs")
+                       else draw(ag.action_space.shape[0])) for ag in env.agents} for _ in range(count)]
+
+
+def ab(label, envs, m):
+    acts = actions(envs[0])
+    ks = [0, 0]
+
+    def run(i, count):
+        e = envs[i]
+        for _ in range(count):
+            _, _, d, _ = e.step(acts[ks[i] % len(acts)])
+            ks[i] += 1
+            if d["__all__"]:
+                e.reset()
+    for i in range(2):
+        envs[i].reset()
+        run(i, min(m, 100))
+    for r in range(rounds):
+        out = []
+        for i in range(2):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            run(i, m)
+            torch.cuda.synchronize()
+            out.append((time.perf_counter() - t0) / m * 1e6)
+        print("%s round %d: general %.2f us/step  fast %.2f us/step  ratio %.3f"
+              % (label, r, out[0], out[1], out[0] / out[1]), flush=True)
+
+
+from powergridworld_amd.scenarios.heterogeneous import make_env_config   # noqa: E402
+
+envs = []
+for mode in MODES:
+    cfg = make_env_config()
+    cfg["pf_config"]["config"].update(yprim="step", step_kernel=mode)
+    envs.append(MultiAgentEnv(**cfg, num_envs=n, device=dev))
+    assert envs[-1].pf_solver.general == (mode == "general") and (envs[-1]._ma is not None) == (mode == "fast")
+ab("HET step", envs, steps)
+del envs
+
+from powergridworld_amd.scenarios.coordinated import CoordinatedMultiBuildingControlEnv, make_c4_config   # noqa: E402
+
+envs = []
+for mode in MODES:
+    cfg = make_c4_config()
+    cfg["pf_config"]["config"].update(yprim="step", step_kernel=mode)
+    envs.append(CoordinatedMultiBuildingControlEnv(**cfg, num_envs=n, device=dev))
+    assert envs[-1]._fused is None and envs[-1]._ma is None
+ab("C4 generic step", envs, max(steps // 4, 24))
+for e, mode in zip(envs, MODES):
+    assert e.pf_solver.general == (mode == "general"), mode
