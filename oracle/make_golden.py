@@ -671,9 +671,233 @@ def gen_hs_order():
           min_voltage=stack("mv"), episodes=np.array(EPISODES))
 
 
+# The house off the shipped scenario (tests/_hs_direct_common.py replays these):
+# synthetic configs that reach what hs_scenario / hs_order never do -- several
+# vehicles charging at once, indices >= 32 and vehicle 63, vehicles departing
+# unserved, a grid cap that binds, grid costs <= 0, device rows that are exact
+# zeros or sit at round(x, 3)'s 0.0005 edge, a storage range narrow enough for
+# both SoC limits, rescale_spaces off, 1 / 2 / 3 / 4 device columns, the chain
+# [pv, devices, storage, ev].  Each fixture holds the whole config as JSON
+# (settings only), so a test rebuilds pgw_hs_params / pgw_hs_step_info from it,
+# and the charging / departed vehicle lists in the reference's own iteration
+# order (CPython's set order, ev_charging_env_hs.py:201-206).
+HS_EDGE_NAMES = {"pv": "HSPVEnv", "storage": "HSEnergyStorageEnv", "ev-charging": "HSEVChargingEnv",
+                 "other-devices": "HSDevicesEnv"}
+HS_EDGE_ACT = {"pv": (0.98, 1.0), "storage": (-1.0, 1.0), "ev-charging": (0.0, 1.0), "other-devices": (0.99, 1.0)}
+HS_EDGE_STEPS = 60
+
+
+def _hs_edge_vehicles(rng, n, active, lo_park, hi_park, pinned=()):
+    """A vehicle table of n rows: the rows in `active` park inside the
+    episode (overlapping windows, parks of lo_park..hi_park minutes: some too
+    short for their energy), the others long after it.  `pinned` rows share
+    one window with at least two others, so they charge together."""
+    T = HS_EDGE_STEPS * 5
+    rows = []
+    for v in range(n):
+        if v in active:
+            start = float(rng.integers(0, T - 40)) + float(rng.choice([0.0, 0.0, 2.5, 4.0]))
+            park = float(rng.integers(lo_park, hi_park))
+            need = float(np.round(rng.uniform(0.3, 6.0), 3))
+        else:
+            start, park, need = 5000.0 + 5 * v, 30.0, 4.0
+        rows.append([start, start + park, need])
+    for k, v in enumerate(pinned):
+        rows[v][0], rows[v][1] = 60.0 + 5.0 * (k % 2), 60.0 + 45.0 + 5.0 * (k % 3)
+    return {"columns": ["start_time_min", "end_time_park_min", "energy_required_kwh"],
+            "index": list(range(n)), "data": rows}
+
+
+def _hs_edge_configs():
+    rng = np.random.default_rng(4242)
+    T = HS_EDGE_STEPS
+    costs = lambda: [float(c) for c in rng.choice([-0.21, -0.05, 0.0, 0.0, 0.25847, 0.46, 0.57098], T)]
+    stamps = [str(t) for t in pd.date_range("2022-06-29 06:00:00", periods=T, freq="5min")]
+
+    def pv_data():
+        d = rng.uniform(0.0, 9.0, T)
+        d[rng.random(T) < 0.3] = 0.0
+        return [float(x) for x in d]
+
+    def devices(ncol, edge=False):
+        d = {}
+        for c in range(ncol):
+            col = rng.uniform(0.0, 0.4, T + 1)
+            col[rng.random(T + 1) < 0.25] = 0.0
+            col[rng.random(T + 1) < 0.2] = rng.uniform(0.0, 0.001 / ncol)     # sums on both sides of 0.0005
+            d["dev%d" % c] = col
+        if edge:
+            # rows whose sum is exactly the edge of round(x, 3) == 0.0 and its two
+            # neighbours (one column holds it, the others exact zeros), and all zeros
+            edges = [0.0005, float(np.nextafter(0.0005, 0.0)), float(np.nextafter(0.0005, 1.0)), 0.0, 0.0004, 0.0006]
+            for k, x in enumerate(edges * 2):
+                row = 3 + 4 * k
+                for c in range(ncol):
+                    d["dev%d" % c][row] = x if c == k % ncol else 0.0
+        return {k: [float(x) for x in v] for k, v in d.items()}
+
+    def comp(name, **config):
+        return {"name": name, "cls": HS_EDGE_NAMES[name], "config": dict(config, minutes_per_step=5)}
+
+    def house(tag, order, max_grid_power, parts):
+        return {"tag": tag, "name": "house", "max_grid_power": max_grid_power, "max_episode_steps": T,
+                "grid_cost": costs(), "timestamps": stamps, "components": [parts[k] for k in order]}
+
+    out = []
+    # a: the shipped order; 33 vehicles of which only rows < 8 ever park; one device column
+    out.append(house("a", ["pv", "storage", "ev-charging", "other-devices"], 48, {
+        "pv": comp("pv", profile_csv="", profile_data=pv_data(), rescale_spaces=True),
+        "storage": comp("storage", max_power=6, storage_range=[3.0, 4.5], charge_efficiency=0.95,
+                        discharge_efficiency=0.9, rescale_spaces=True, initial_storage_cost=0.25847,
+                        max_storage_cost=0.57098),
+        "ev-charging": comp("ev-charging", num_vehicles=8, max_charge_rate_kw=7.0, rescale_spaces=True,
+                            max_charge_cost=0.57098, unserved_penalty=1.0,
+                            profile_data=_hs_edge_vehicles(rng, 33, set(range(8)), 10, 45, pinned=(1, 4, 6))),
+        "other-devices": comp("other-devices", profile_csv="", profile_data=devices(1), rescale_spaces=True)}))
+    # b: hs_order's chain with a grid-aware PV; 64 vehicles, rows up to 63 park; three device
+    # columns; the EV and the storage take raw actions
+    out.append(house("b", ["pv", "ev-charging", "other-devices", "storage"], 400, {
+        "pv": comp("pv", profile_csv="", profile_data=pv_data(), rescale_spaces=True, grid_aware=True),
+        "storage": comp("storage", max_power=15.0, storage_range=[3.0, 50.0], charge_efficiency=0.93,
+                        discharge_efficiency=0.87, rescale_spaces=False, initial_storage_cost=0.1,
+                        max_storage_cost=0.55),
+        "ev-charging": comp("ev-charging", num_vehicles=64, max_charge_rate_kw=7.0, rescale_spaces=False,
+                            max_charge_cost=0.55, unserved_penalty=0.5, vehicle_multiplier=2,
+                            profile_data=_hs_edge_vehicles(rng, 64, set(range(64)), 10, 60,
+                                                           pinned=(31, 32, 63, 40, 57, 35, 9))),
+        "other-devices": comp("other-devices", profile_csv="", profile_data=devices(3), rescale_spaces=True)}))
+    # c: [pv, devices, storage, ev]; a 3 kW grid cap that the storage and the EV exhaust (the EV
+    # last: its cost is guarded by `sum > 0`); four device columns with the round(x, 3) edges and
+    # a raw device action; a raw PV action; a narrow storage range
+    out.append(house("c", ["pv", "other-devices", "storage", "ev-charging"], 3, {
+        "pv": comp("pv", profile_csv="", profile_data=pv_data(), rescale_spaces=False),
+        "storage": comp("storage", max_power=15.0, storage_range=[3.0, 5.0], charge_efficiency=0.95,
+                        discharge_efficiency=0.95, rescale_spaces=True, initial_storage_cost=0.0,
+                        max_storage_cost=0.55),
+        "ev-charging": comp("ev-charging", num_vehicles=16, max_charge_rate_kw=11.0, rescale_spaces=True,
+                            max_charge_cost=0.55, unserved_penalty=1.0,
+                            profile_data=_hs_edge_vehicles(rng, 64, set(range(0, 64, 2)) | {31, 63}, 10, 40,
+                                                           pinned=(31, 32, 63, 62, 8))),
+        "other-devices": comp("other-devices", profile_csv="", profile_data=devices(4, edge=True),
+                              rescale_spaces=False)}))
+    # d: the shipped order, nothing rescaled; 33 vehicles, every row parks; two device columns
+    out.append(house("d", ["pv", "storage", "ev-charging", "other-devices"], 400, {
+        "pv": comp("pv", profile_csv="", profile_data=pv_data(), rescale_spaces=False, grid_aware=True),
+        "storage": comp("storage", max_power=6.0, storage_range=[0.5, 2.0], charge_efficiency=0.95,
+                        discharge_efficiency=0.95, rescale_spaces=False, initial_storage_cost=0.3,
+                        max_storage_cost=0.57098),
+        "ev-charging": comp("ev-charging", num_vehicles=33, max_charge_rate_kw=7.0, rescale_spaces=False,
+                            max_charge_cost=0.57098, unserved_penalty=2.0,
+                            profile_data=_hs_edge_vehicles(rng, 33, set(range(33)), 10, 50, pinned=(32, 8, 16, 24))),
+        "other-devices": comp("other-devices", profile_csv="", profile_data=devices(2, edge=True),
+                              rescale_spaces=False)}))
+    return out
+
+
+def gen_hs_edges():
+    import gridworld.agents.devices as rdev
+    import gridworld.agents.energy_storage as rsto
+    import gridworld.agents.pv as rpv
+    import gridworld.agents.vehicles as rveh
+    from gridworld import HSMultiComponentEnv
+    classes = {"HSPVEnv": rpv.HSPVEnv, "HSEnergyStorageEnv": rsto.HSEnergyStorageEnv,
+               "HSEVChargingEnv": rveh.HSEVChargingEnv, "HSDevicesEnv": rdev.HSDevicesEnv}
+    K, EPISODES = 3, 2
+    for ci, cfg in enumerate(_hs_edge_configs()):
+        rng = np.random.default_rng(5150 + ci)
+        text = json.dumps(cfg)                      # what the fixture holds: rebuilt from it below
+        names = [c["name"] for c in cfg["components"]]
+        rescale = [bool(c["config"]["rescale_spaces"]) for c in cfg["components"]]
+        aware = any(c["config"].get("grid_aware") for c in cfg["components"])
+        n_veh = len(cfg["components"][names.index("ev-charging")]["config"]["profile_data"]["data"])
+        dev_slot = names.index("other-devices")
+        runs = []
+        for k in range(K):
+            live = json.loads(text)
+            live.pop("tag")
+            for c in live["components"]:
+                c["cls"] = classes[c["cls"]]
+            env = HSMultiComponentEnv(**live)
+            ev, sto, dev = env.env_dict["ev-charging"], env.env_dict["storage"], env.env_dict["other-devices"]
+            rec = dict(obs=[], act=[], rew=[], rp=[], done=[], meta=[], soc=[], smeta=[], sts=[], mv=[], init=[],
+                       chg=[], dep=[], req=[], costs=[])
+
+            def state():
+                pad = lambda l: [int(i) for i in l] + [-1] * (n_veh - len(l))
+                rec["chg"].append(pad(ev.charging_vehicles))
+                rec["dep"].append(pad(ev.departed_vehicles))
+                rec["req"].append(np.array(ev.df["energy_required_kwh"], dtype=np.float64, copy=True))
+                rec["costs"].append([float(sto.current_cost), float(getattr(ev, "current_cost", 0.0)),
+                                     float(getattr(dev, "current_cost", 0.0))])
+                rec["soc"].append(float(sto.current_storage))
+
+            for ep in range(EPISODES):
+                lo, hi = sto.storage_range
+                init = float(rng.uniform(lo - 0.3, hi + 0.3))
+                mv = float(rng.uniform(0.88, 1.12))
+                rec["init"].append(init)
+                rec["mv"].append(mv)
+                with quiet():
+                    o = env.reset(init_storage=init, **({"min_voltage": mv} if aware else {}))
+                rec["obs"].append(np.concatenate([np.ravel(o[n]) for n in names]))
+                rec["meta"].append([np.nan] * 3)
+                state()
+                while True:
+                    a = rng.uniform(-1.1, 1.1, len(names))
+                    a[rng.random(len(names)) < 0.05] = 0.0
+                    a[rng.random(len(names)) < 0.04] = -1.0
+                    a[rng.random(len(names)) < 0.04] = 1.0
+                    for i, n in enumerate(names):
+                        if not rescale[i]:          # a raw action, inside the component's own box
+                            l, h = HS_EDGE_ACT[n]
+                            a[i] = l + (np.clip(a[i], -1.0, 1.0) + 1.0) / 2.0 * (h - l)
+                    if not rescale[dev_slot] and k < 2:
+                        a[dev_slot] = 1.0           # exactly the row's sum: the 0.0005 edge rows
+                    mv = float(rng.uniform(0.88, 1.12))
+                    with quiet():
+                        o, r, d, m = env.step({n: a[i:i + 1].copy() for i, n in enumerate(names)},
+                                              **({"min_voltage": mv} if aware else {}))
+                    rec["act"].append(a)
+                    rec["mv"].append(mv)
+                    rec["obs"].append(np.concatenate([np.ravel(o[n]) for n in names]))
+                    rec["rew"].append(float(r))
+                    rec["rp"].append(float(env.real_power))
+                    rec["done"].append(bool(d))
+                    rec["meta"].append([m["pv_power"], m["es_power"], m["grid_power"]])
+                    sm = np.full((len(names), HS_META_FIELDS), np.nan)
+                    assert [q["device_id"] for q in m["step_meta"]] == names
+                    keys = []
+                    for c, q in enumerate(m["step_meta"]):
+                        vals = [q["cost"], q["reward"], q["action"][0], q["solar_power_consumed"],
+                                q["es_power_consumed"], q["grid_power_consumed"]]
+                        vals += list(q["device_custom_info"].values())
+                        sm[c, :len(vals)] = vals
+                        keys.append(",".join(q["device_custom_info"].keys()))
+                    rec["smeta"].append(sm)
+                    rec["sts"].append(str(m["timestamp"]))
+                    state()
+                    if d:
+                        break
+            runs.append(rec)
+        stack = lambda key: np.stack([np.asarray(r[key], dtype=np.float64) for r in runs], 1)
+        istack = lambda key: np.stack([np.asarray(r[key], dtype=np.int64) for r in runs], 1)
+        T = len(runs[0]["rew"])
+        assert T == EPISODES * HS_EDGE_STEPS and all(len(r["rew"]) == T for r in runs)
+        # the reference alone completed, and nowhere did it divide 0 by 0 into a NaN
+        for key in ("obs", "rew", "rp", "soc", "costs", "req"):
+            assert np.isfinite(stack(key)).all(), (cfg["tag"], key)
+        assert np.isfinite(stack("meta")[[t for t in range(T + EPISODES) if t % (HS_EDGE_STEPS + 1)]]).all()
+        _save("hs_edges_" + cfg["tag"], names=np.array(names), config_json=np.array(text), actions=stack("act"),
+              obs=stack("obs"), reward=stack("rew"), real_power=stack("rp"), done=stack("done").astype(bool),
+              meta=stack("meta"), soc=stack("soc"), episodes=np.array(EPISODES), step_meta=stack("smeta"),
+              step_meta_timestamp=np.array(runs[0]["sts"]), step_meta_custom_keys=np.array(keys),
+              init_storage=stack("init"), min_voltage=stack("mv"), charging=istack("chg"), departed=istack("dep"),
+              ev_req=stack("req"), costs=stack("costs"))
+
+
 GENERATORS = {"battery": gen_battery, "pv": gen_pv, "building": gen_building,
               "ev": gen_ev, "evrand": gen_ev_random, "mc": gen_mc, "c4": gen_c4, "c4ep": gen_c4_episodes,
-              "het": gen_het, "hs": gen_hs, "hs_order": gen_hs_order,
+              "het": gen_het, "hs": gen_hs, "hs_order": gen_hs_order, "hs_edges": gen_hs_edges,
               # the reference's own power-flow rule (OpenDSS's snap solve, opendss.py:131-135)
               # through the reference's MultiAgentEnv: the same seeded action streams
               "c4_od": lambda: gen_c4("opendss"), "c4ep_od": lambda: gen_c4_episodes("opendss"),
