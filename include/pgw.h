@@ -1031,6 +1031,37 @@ int32_t pgw_coord_step_f32(const pgw_coord_params* p, const pgw_pf_params* pf,
                            const pgw_pf_tables* pft, const pgw_coord_step_info* s, int64_t n,
                            pgw_coord_buffers_f32 b, void* stream);
 
+/* The coordinated step under OpenDSSSolver yprim="step" (H1, pgw_pf_solve_h1's
+ * map): two launches on the stream, the agents' kernel pgw_coord_step picks for
+ * the layout (fp64: the standard C4 layout or any other; fp32: the standard one
+ * only, env pairs per lane where n and the strides are even), then
+ * k_coord_pf_od_h1, one lane per env:
+ *   bus load     P = 0 + p_0 + p_1 + ... over the agents with agent_ctrl = 0, in
+ *                agent order, from agent_power widened to double; Q = 0 (an
+ *                agent with agent_ctrl = -1 adds nothing; n_ctrl = 0: K = 0);
+ *   solve        pgw_pf_solve_h1's, with pft and h as that entry reads them (no
+ *                response table, no first-iteration table: every env is solved);
+ *   outputs      v_out [n_out x n] (row p->vv_row the coordinated bus), iters
+ *                (-it where max_iter stopped the env), pft->v_min_out /
+ *                v_max_out over the n_out rows if set, all nullable;
+ *   coordinated  vv = max(max(0, vv_lo - v), v - vv_hi) at row vv_row into vv
+ *                (nullable), reward[a] = reward[a] + (-(vv vv_penalty / n_agents))
+ *                in the storage type; nothing of it with coordinated = 0.
+ * Bit-identical to the agents' entries, pgw_agent_reduce, pgw_pf_solve_h1 and
+ * the host's reward transform.  od_list is not read; od_count, if set, has the
+ * next step's counter zeroed.  PGW_ERR_ARG, before any launch, for everything
+ * pgw_coord_step refuses and everything pgw_pf_solve_h1 refuses: pft->od NULL; a
+ * shape other than m = 14 with one voltage band; n_ctrl > 1; n_ctrl = 1 with
+ * more or fewer than one element on slot 0 or h->elem not that element; U_init;
+ * load_scale; od resp / resp_v / resp_q / start.  h: HOST pointer. */
+int32_t pgw_coord_step_h1(const pgw_coord_params* p, const pgw_pf_params* pf, const pgw_pf_tables* pft,
+                          const pgw_pf_h1* h, const pgw_coord_step_info* s, int64_t n, pgw_coord_buffers b,
+                          void* stream);
+/* fp32-storage variant, as pgw_coord_step_f32 (the solve and the extrema fp64). */
+int32_t pgw_coord_step_h1_f32(const pgw_coord_params* p, const pgw_pf_params* pf, const pgw_pf_tables* pft,
+                              const pgw_pf_h1* h, const pgw_coord_step_info* s, int64_t n,
+                              pgw_coord_buffers_f32 b, void* stream);
+
 /* ------------------------------------------------------------------------
  * Fused MultiComponentEnv step (SURVEY 8(b) pgw_mc_agent_step): one agent of
  * building / PV / storage / EV components (each at most once, any order) --

@@ -387,6 +387,10 @@ _SIGS = {
                                  CoordBuffersF32, vp]),
     "pgw_coord_step_general": (i32, [P(CoordParams), P(PFGParams), P(PFGTables), P(CoordStepInfo), i64,
                                      CoordBuffers, vp]),
+    "pgw_coord_step_h1": (i32, [P(CoordParams), P(PFParams), P(PFTables), P(PFH1), P(CoordStepInfo), i64,
+                                CoordBuffers, vp]),
+    "pgw_coord_step_h1_f32": (i32, [P(CoordParams), P(PFParams), P(PFTables), P(PFH1), P(CoordStepInfo), i64,
+                                    CoordBuffersF32, vp]),
     "pgw_hs_reset": (i32, [P(HSParams), P(HSStepInfo), i64, vp, HSBuffers, vp]),
     "pgw_mc_agent_step": (i32, [P(MCStepArgs), i64, vp]),
     "pgw_mc_agent_step_f32": (i32, [P(MCStepArgsF32), i64, vp]),

@@ -3309,6 +3309,77 @@ __global__ void __launch_bounds__(kBlock) k_pf_solve_od_h1(PFArgs a, ODArgs o, H
   if (iters) iters[e] = it;
 }
 
+// Fused C4 step under yprim = "step" (pgw_coord_step_h1): k_pf_solve_od_h1's
+// solve between coord_pf_od_env's prologue (agent powers -> the load of slot 0,
+// 0 + p0 + p1 ... in agent order) and epilogue (violation at the coordinated
+// bus, reward = raw + (-share)).  No response table: every env solves.  The
+// agents' rewards are loaded behind the solve with the output rows (as
+// k_pf_solve_od_ms's row loads: the solve has no registers to hold them), their
+// latency under od_load_J and pf_node0.  Bit-identical to the agents' kernel,
+// pgw_agent_reduce, pgw_pf_solve_h1 and the host's reward transform.
+template <int M, class Bufs>
+__global__ void __launch_bounds__(kBlock) k_coord_pf_od_h1(CoordPFArgs c, PFArgs a, ODArgs o, H1Args h,
+                                                           pgw_pf_tables t, int64_t n, Bufs b) {
+  using Sto = std::remove_pointer_t<decltype(b.reward)>;
+  const int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  const bool valid = e < n;
+  const int64_t ec = valid ? e : 0;
+  __shared__ ODShared<M> sh;
+  ODStage<M> stg;
+  const bool rows_lds = od_rows_lds<M>(a.n_out);     // (uniform) a history slot: every node
+  PFSolverH1<M> S;
+  od_stage_load<M, false>(o, nullptr, stg);
+  S.load(a, t.block);
+  double pc = 0.0;
+#pragma unroll
+  for (int ag = 0; ag < PGW_MAX_AGENTS; ++ag) {
+    const double rp = (double)b.agent_power[(int64_t)min(ag, c.n_agents - 1) * n + ec] *
+                      ((valid && ag < c.n_agents) ? 1.0 : 0.0);
+    const int slot = ag < c.n_agents ? c.agent_ctrl[ag] : -1;
+    pc = (slot == 0) ? pc + rp : pc;
+  }
+  S.pc = valid ? pc : 0.0;
+  S.qc = 0.0;
+  S.set_h1(h);
+  od_stage_store<M, false>(o, stg, sh);
+  od_first_h1<M>(S, sh);                             // (reads no staged LDS)
+  __syncthreads();                                   // the staged check rows
+  int it = 0;
+  if (__ballot(valid) != 0ull)                       // (wave-uniform) some env of this wave
+    it = od_solve<M, false, PFSolverH1<M>>(S, o, stg, valid, sh);
+  double rv[kOdRowQ];
+  if (rows_lds) od_rows_issue<M>(t, a.n_out, rv);
+  Sto rw[PGW_MAX_AGENTS];
+#pragma unroll
+  for (int ag = 0; ag < PGW_MAX_AGENTS; ++ag)
+    rw[ag] = (c.coordinated && ag < c.n_agents) ? b.reward[(int64_t)ag * n + ec] : (Sto)0;
+  double ir[M], ii[M], v0r = 0.0, v0i = 0.0;
+  od_load_J<M>(sh, it, ir, ii);
+  pf_node0<M>(v0r, v0i, S.w, ir, ii);
+  const double v0 = sqrt(fma(v0i, v0i, v0r * v0r));
+  double vsel = v0, vmn = v0, vmx = v0;              // Python min()/max() over the rows in order
+  const double* srow = rows_lds ? od_rows_put<M>(sh, a.n_out, rv) : nullptr;
+  pf_rows_out<M>(t, rows_lds, srow, a.n_out, ir, ii, [&](int ro, double v) {
+    if (valid && b.v_out) b.v_out[(int64_t)ro * n + e] = (Sto)v;
+    vsel = (ro == c.vv_row) ? v : vsel;
+    vmn = (v < vmn) ? v : vmn;
+    vmx = (v > vmx) ? v : vmx;
+  });
+  if (!valid) return;
+  if (b.v_out) b.v_out[e] = (Sto)v0;
+  if (t.v_min_out) t.v_min_out[e] = vmn;
+  if (t.v_max_out) t.v_max_out[e] = vmx;
+  if (b.iters) b.iters[e] = it;
+  if (c.coordinated) {
+    const double vv = pymax(pymax(0.0, c.vv_lo - vsel), vsel - c.vv_hi);
+    if (b.vv) b.vv[e] = (Sto)vv;
+    const double share = (vv * c.vv_penalty) / (double)c.n_agents;
+#pragma unroll
+    for (int ag = 0; ag < PGW_MAX_AGENTS; ++ag)
+      if (ag < c.n_agents) b.reward[(int64_t)ag * n + e] = (Sto)(rw[ag] + (Sto)(-share));
+  }
+}
+
 // Response-table builder (pgw_pf_od_probe): the snap solve at lane e's kW P[e]
 // (Q = 0) in hour e / lanes_per_hour -- that hour's PFArgs (base loads) and
 // first-iteration table -- with the signature of its pieces.
@@ -3709,17 +3780,62 @@ __global__ void k_step_nop(int* p) {
 }
 
 // pgw_coord_step / pgw_coord_step_f32
-// The agents' half of the coordinated step (k_coord_agents_std or the generic
-// k_coord_agents), fp64 buffers.
+// The agents' half of the coordinated step on either storage type
+// (pgw_coord_step, pgw_coord_step_general, pgw_coord_step_h1): k_coord_agents_std
+// or the generic k_coord_agents; fp32 takes env pairs per lane (float2
+// accesses) where pairs_ok.  The pair layout measured for fp64 too (19.5 ->
+// 20.2 us), so it is instantiated for fp32 only; fp32 has the standard layout
+// alone (the callers check).
+template <class Bufs>
 static int32_t launch_coord_agents(const pgw_coord_params& p, const pgw_coord_step_info& s, int64_t n,
-                                   const pgw_coord_buffers& b, double pv_ob, bool std_layout, hipStream_t st) {
-  if (std_layout)
-    launch_timed(PGW_T_COORD_AGENTS, k_coord_agents_std<pgw_coord_buffers>, dim3(grid_for(n), p.n_agents),
+                                   const Bufs& b, double pv_ob, bool std_layout, hipStream_t st) {
+  constexpr bool kF32 = std::is_same<Bufs, pgw_coord_buffers_f32>::value;
+  bool done = false;
+  if constexpr (kF32) {
+    if (std_layout && pairs_ok(b, n)) {
+      launch_timed(PGW_T_COORD_AGENTS, k_coord_agents_std_x2<Bufs>, dim3(grid_for(n / 2), p.n_agents),
+                   dim3(kBlock), st, p, s, n, b, pv_ob, make_std_derived(p));
+      done = true;
+    }
+  }
+  if (done) {
+  } else if (std_layout) {
+    launch_timed(PGW_T_COORD_AGENTS, k_coord_agents_std<Bufs>, dim3(grid_for(n), p.n_agents),
                  dim3(kBlock), st, p, s, n, b, pv_ob, make_std_derived(p));
-  else
-    launch_timed(PGW_T_COORD_AGENTS, k_coord_agents, dim3(grid_for(n), p.n_agents), dim3(kBlock), st, p, s, n,
-                 b);
+  } else if constexpr (!kF32) {
+    launch_timed(PGW_T_COORD_AGENTS, k_coord_agents, dim3(grid_for(n), p.n_agents), dim3(kBlock),
+                 st, p, s, n, b);
+  }
   return check_launch("k_coord_agents");
+}
+
+// pgw_coord_step's argument checks (who: the entry's name in the messages).
+template <class Bufs>
+static int32_t check_coord(const char* who, const pgw_coord_params* p, const pgw_pf_params* pf,
+                           const pgw_pf_tables* pft, const pgw_coord_step_info* s, int64_t n, const Bufs& b) {
+  PGW_REQUIRE(p && pf && pft && s && n >= 0, "%s: null argument", who);
+  PGW_REQUIRE(p->n_agents >= 1 && p->n_agents <= PGW_MAX_AGENTS, "%s: bad n_agents", who);
+  PGW_REQUIRE(p->n_comp >= 1 && p->n_comp <= 3, "%s: bad n_comp", who);
+  PGW_REQUIRE(b.action.ptr && b.obs.ptr && b.reward && b.agent_power,
+              "%s: null buffer", who);
+  PGW_REQUIRE(pft->block, "%s: null PF block", who);
+  PGW_REQUIRE(!pft->load_scale && !pft->U_init, "%s: load_scale / U_init not supported", who);
+  PGW_REQUIRE(pf->m >= 1 && pf->m <= PGW_PF_MAX_M && pf->m == padded_m(pf->m),
+              "%s: pf m=%d not padded", who, pf->m);
+  PGW_REQUIRE(pf->n_out >= 1 && p->vv_row >= 0 && p->vv_row < pf->n_out,
+              "%s: bad vv_row", who);
+  PGW_REQUIRE(pft->G && pft->V0, "%s: missing G/V0", who);
+  PGW_REQUIRE(pf->max_iter >= 1, "%s: max_iter < 1", who);
+  PGW_REQUIRE(pf->n_ctrl >= 0 && pf->n_ctrl <= PGW_PF_MAX_CTRL, "%s: bad n_ctrl", who);
+  for (int a = 0; a < p->n_agents; ++a)
+    PGW_REQUIRE(p->agent_ctrl[a] < pf->n_ctrl, "%s: agent_ctrl out of range", who);
+  for (int c = 0; c < p->n_comp; ++c) {
+    int k = p->comp_order[c];
+    PGW_REQUIRE(k >= 0 && k <= 2, "%s: bad comp_order", who);
+    if (k == 0) PGW_REQUIRE(b.x && p->act_bld >= 0 && p->bld.n_obs <= PGW_BLD_MAX_OBS, "%s: building", who);
+    if (k == 2) PGW_REQUIRE(b.soc && p->act_bat >= 0, "%s: storage", who);
+  }
+  return PGW_OK;
 }
 
 // The agents' kernel, then the power flow with the coordinated prologue and
@@ -3728,28 +3844,8 @@ template <class Bufs>
 static int32_t coord_step(const pgw_coord_params* p, const pgw_pf_params* pf, const pgw_pf_tables* pft,
                           const pgw_coord_step_info* s, int64_t n, const Bufs& b, void* stream) {
   constexpr bool kF32 = std::is_same<Bufs, pgw_coord_buffers_f32>::value;
-  PGW_REQUIRE(p && pf && pft && s && n >= 0, "pgw_coord_step: null argument");
-  PGW_REQUIRE(p->n_agents >= 1 && p->n_agents <= PGW_MAX_AGENTS, "pgw_coord_step: bad n_agents");
-  PGW_REQUIRE(p->n_comp >= 1 && p->n_comp <= 3, "pgw_coord_step: bad n_comp");
-  PGW_REQUIRE(b.action.ptr && b.obs.ptr && b.reward && b.agent_power,
-              "pgw_coord_step: null buffer");
-  PGW_REQUIRE(pft->block, "pgw_coord_step: null PF block");
-  PGW_REQUIRE(!pft->load_scale && !pft->U_init, "pgw_coord_step: load_scale / U_init not supported");
-  PGW_REQUIRE(pf->m >= 1 && pf->m <= PGW_PF_MAX_M && pf->m == padded_m(pf->m),
-              "pgw_coord_step: pf m=%d not padded", pf->m);
-  PGW_REQUIRE(pf->n_out >= 1 && p->vv_row >= 0 && p->vv_row < pf->n_out,
-              "pgw_coord_step: bad vv_row");
-  PGW_REQUIRE(pft->G && pft->V0, "pgw_coord_step: missing G/V0");
-  PGW_REQUIRE(pf->max_iter >= 1, "pgw_coord_step: max_iter < 1");
-  PGW_REQUIRE(pf->n_ctrl >= 0 && pf->n_ctrl <= PGW_PF_MAX_CTRL, "pgw_coord_step: bad n_ctrl");
-  for (int a = 0; a < p->n_agents; ++a)
-    PGW_REQUIRE(p->agent_ctrl[a] < pf->n_ctrl, "pgw_coord_step: agent_ctrl out of range");
-  for (int c = 0; c < p->n_comp; ++c) {
-    int k = p->comp_order[c];
-    PGW_REQUIRE(k >= 0 && k <= 2, "pgw_coord_step: bad comp_order");
-    if (k == 0) PGW_REQUIRE(b.x && p->act_bld >= 0 && p->bld.n_obs <= PGW_BLD_MAX_OBS, "pgw_coord_step: building");
-    if (k == 2) PGW_REQUIRE(b.soc && p->act_bat >= 0, "pgw_coord_step: storage");
-  }
+  const int32_t rc_args = check_coord("pgw_coord_step", p, pf, pft, s, n, b);
+  if (rc_args) return rc_args;
   if (n == 0) return PGW_OK;
   hipStream_t st = (hipStream_t)stream;
   const bool std_layout = coord_is_std(*p);
@@ -3844,25 +3940,7 @@ static int32_t coord_step(const pgw_coord_params* p, const pgw_pf_params* pf, co
       PGW_REQUIRE(me == hipSuccess, "pgw_coord_step_f32: od_count reset: %s", hipGetErrorString(me));
     }
   }
-  // fp32: env pairs per lane (float2 accesses).  The pair layout measured for
-  // fp64 too (19.5 -> 20.2 us), so it is instantiated for fp32 only.
-  bool done = false;
-  if constexpr (kF32) {
-    if (std_layout && pairs_ok(b, n)) {
-      launch_timed(PGW_T_COORD_AGENTS, k_coord_agents_std_x2<Bufs>, dim3(grid_for(n / 2), p->n_agents),
-                   dim3(kBlock), st, *p, *s, n, b, pv_ob, make_std_derived(*p));
-      done = true;
-    }
-  }
-  if (done) {
-  } else if (std_layout) {
-    launch_timed(PGW_T_COORD_AGENTS, k_coord_agents_std<Bufs>, dim3(grid_for(n), p->n_agents),
-                 dim3(kBlock), st, *p, *s, n, b, pv_ob, make_std_derived(*p));
-  } else if constexpr (!kF32) {
-    launch_timed(PGW_T_COORD_AGENTS, k_coord_agents, dim3(grid_for(n), p->n_agents), dim3(kBlock),
-                 st, *p, *s, n, b);
-  }
-  int32_t rc = check_launch("k_coord_agents");
+  int32_t rc = launch_coord_agents(*p, *s, n, b, pv_ob, std_layout, st);
   if (rc) return rc;
   if (g_step_nop) hipLaunchKernelGGL(k_step_nop, dim3(1), dim3(64), 0, st, (int*)nullptr);
   hipStream_t pst = st;
@@ -4137,47 +4215,100 @@ static int32_t pf_solve(const pgw_pf_params* p, const pgw_pf_tables* t, int64_t 
 
 // pgw_pf_solve_h1 / pgw_pf_solve_h1_f32
 static_assert(sizeof(pgw_pf_h1) == 8 + 16 * PGW_PF_MAX_M && offsetof(pgw_pf_h1, wc) == 8, "pgw_pf_h1 layout");
+// The H1 entries' checks of the solve's shape (who: the entry's name).
+static int32_t check_h1(const char* who, const pgw_pf_params* p, const pgw_pf_tables* t, const pgw_pf_h1* h) {
+  PGW_REQUIRE(t->od, "%s: tables without od (the OpenDSS rule's check rows)", who);
+  const pgw_pf_od* d = t->od;
+  PGW_REQUIRE(p->m == 14 && uniform_band(*p), "%s: needs the fast shape, m = 14 and one voltage band "
+              "(use pgw_pf_solve_general with PGW_PF_OPENDSS_STEP)", who);
+  PGW_REQUIRE(p->n_ctrl >= 0 && p->n_ctrl <= 1, "%s: %d controllable slots (at most one)", who, p->n_ctrl);
+  PGW_REQUIRE(!t->U_init && !t->load_scale, "%s: takes no U_init / load_scale", who);
+  PGW_REQUIRE(!d->resp && !d->resp_v && !d->resp_q,
+              "%s: takes no response table (od resp / resp_v / resp_q must be NULL)", who);
+  int on0 = 0;
+  for (int k = 0; k < p->m; ++k) on0 += p->elem_ctrl[k] == 0;
+  PGW_REQUIRE(p->n_ctrl == 0 || (on0 == 1 && h->elem >= 0 && h->elem < p->m && p->elem_ctrl[h->elem] == 0),
+              "%s: slot 0 must hold exactly one element, pgw_pf_h1.elem (%d elements, elem %d)", who, on0,
+              h->elem);
+  PGW_REQUIRE(p->n_out == 0 || (t->G && t->V0), "%s: missing G/V0", who);
+  PGW_REQUIRE(d->n_rows >= 0 && d->n_rows <= PGW_PF_OD_MAX_ROWS && d->n_rep >= 0 && d->n_rep <= d->n_rows,
+              "%s: od n_rep %d / n_rows %d (<= %d)", who, d->n_rep, d->n_rows, PGW_PF_OD_MAX_ROWS);
+  // (the stage's loads issue unconditionally: one dummy row when n_rows = 0)
+  PGW_REQUIRE(d->rows_V0 && d->rows_G, "%s: od rows missing", who);
+  PGW_REQUIRE(d->min_iter >= 2 && p->max_iter >= 1 && d->tol >= 0.0, "%s: od min_iter / max_iter / tol", who);
+  return PGW_OK;
+}
+
+static H1Args make_h1_args(const pgw_pf_params& p, const pgw_pf_h1& h) {
+  H1Args ha = {};
+  ha.c = p.n_ctrl == 1 ? h.elem : -1;
+  ha.nph = 1.0;
+  if (ha.c >= 0) {
+    for (int k = 0; k < p.m; ++k) {
+      ha.wcr[k] = h.wc[2 * k];
+      ha.wci[k] = h.wc[2 * k + 1];
+    }
+    ha.wccr = ha.wcr[ha.c];
+    ha.wcci = ha.wci[ha.c];
+    ha.nph = p.nph[ha.c];
+  }
+  return ha;
+}
+
 template <class IO>
 static int32_t pf_solve_h1(const pgw_pf_params* p, const pgw_pf_tables* t, const pgw_pf_h1* h, int64_t n,
                            const IO* ctrl_p, const IO* ctrl_q, IO* v_out, int32_t* iters, void* stream) {
   PGW_REQUIRE(p && t && h && t->block && n >= 0, "pgw_pf_solve_h1: null argument");
-  PGW_REQUIRE(t->od, "pgw_pf_solve_h1: tables without od (the OpenDSS rule's check rows)");
-  const pgw_pf_od* d = t->od;
-  PGW_REQUIRE(p->m == 14 && uniform_band(*p), "pgw_pf_solve_h1: needs the fast shape, m = 14 and one voltage band "
-              "(use pgw_pf_solve_general with PGW_PF_OPENDSS_STEP)");
-  PGW_REQUIRE(p->n_ctrl >= 0 && p->n_ctrl <= 1, "pgw_pf_solve_h1: %d controllable slots (at most one)", p->n_ctrl);
-  PGW_REQUIRE(!t->U_init && !t->load_scale, "pgw_pf_solve_h1: takes no U_init / load_scale");
-  PGW_REQUIRE(!d->resp && !d->resp_v && !d->resp_q,
-              "pgw_pf_solve_h1: takes no response table (od resp / resp_v / resp_q must be NULL)");
-  int on0 = 0;
-  for (int k = 0; k < p->m; ++k) on0 += p->elem_ctrl[k] == 0;
-  PGW_REQUIRE(p->n_ctrl == 0 || (on0 == 1 && h->elem >= 0 && h->elem < p->m && p->elem_ctrl[h->elem] == 0),
-              "pgw_pf_solve_h1: slot 0 must hold exactly one element, pgw_pf_h1.elem (%d elements, elem %d)", on0,
-              h->elem);
-  PGW_REQUIRE(p->n_out == 0 || (t->G && t->V0), "pgw_pf_solve_h1: missing G/V0");
+  const int32_t rc = check_h1("pgw_pf_solve_h1", p, t, h);
+  if (rc) return rc;
   PGW_REQUIRE(p->n_out == 0 || v_out || t->v_min_out || t->v_max_out,
               "pgw_pf_solve_h1: n_out > 0 but no output (v_out, v_min_out, v_max_out all NULL)");
-  PGW_REQUIRE(d->n_rows >= 0 && d->n_rows <= PGW_PF_OD_MAX_ROWS && d->n_rep >= 0 && d->n_rep <= d->n_rows,
-              "pgw_pf_solve_h1: od n_rep %d / n_rows %d (<= %d)", d->n_rep, d->n_rows, PGW_PF_OD_MAX_ROWS);
-  // (the stage's loads issue unconditionally: one dummy row when n_rows = 0)
-  PGW_REQUIRE(d->rows_V0 && d->rows_G, "pgw_pf_solve_h1: od rows missing");
-  PGW_REQUIRE(d->min_iter >= 2 && p->max_iter >= 1 && d->tol >= 0.0, "pgw_pf_solve_h1: od min_iter / max_iter / tol");
   if (n == 0) return PGW_OK;
-  H1Args ha = {};
-  ha.c = p->n_ctrl == 1 ? h->elem : -1;
-  ha.nph = 1.0;
-  if (ha.c >= 0) {
-    for (int k = 0; k < p->m; ++k) {
-      ha.wcr[k] = h->wc[2 * k];
-      ha.wci[k] = h->wc[2 * k + 1];
-    }
-    ha.wccr = ha.wcr[ha.c];
-    ha.wcci = ha.wci[ha.c];
-    ha.nph = p->nph[ha.c];
-  }
   launch_timed(PGW_T_PF_SOLVE, k_pf_solve_od_h1<14, IO>, dim3(grid_for(n)), dim3(kBlock), (hipStream_t)stream,
-               make_pf_args(*p, *t), make_od_args(*d, p->max_iter), ha, *t, n, ctrl_p, ctrl_q, v_out, iters);
+               make_pf_args(*p, *t), make_od_args(*t->od, p->max_iter), make_h1_args(*p, *h), *t, n, ctrl_p, ctrl_q,
+               v_out, iters);
   return check_launch("k_pf_solve_od_h1");
+}
+
+// pgw_coord_step_h1 / pgw_coord_step_h1_f32: the agents' kernel coord_step
+// picks for the layout, then k_coord_pf_od_h1, on one stream.
+template <class Bufs>
+static int32_t coord_step_h1(const pgw_coord_params* p, const pgw_pf_params* pf, const pgw_pf_tables* pft,
+                             const pgw_pf_h1* h, const pgw_coord_step_info* s, int64_t n, const Bufs& b,
+                             void* stream) {
+  constexpr bool kF32 = std::is_same<Bufs, pgw_coord_buffers_f32>::value;
+  const char* who = kF32 ? "pgw_coord_step_h1_f32" : "pgw_coord_step_h1";
+  int32_t rc = check_coord(who, p, pf, pft, s, n, b);
+  if (rc) return rc;
+  PGW_REQUIRE(h, "%s: null pgw_pf_h1", who);
+  rc = check_h1(who, pf, pft, h);
+  if (rc) return rc;
+  PGW_REQUIRE(!pft->od->start, "%s: takes no first-iteration table (od start must be NULL)", who);
+  const bool std_layout = coord_is_std(*p);
+  PGW_REQUIRE(std_layout || !kF32, "%s: needs the standard C4 agent layout (building/pv/storage at 0/6/7)", who);
+  if (n == 0) return PGW_OK;
+  hipStream_t st = (hipStream_t)stream;
+  // a step with a list: the next step's count (k_coord_step_od's job) zeroed here
+  if (b.od_count) {
+    const hipError_t me = hipMemsetAsync(b.od_count + ((b.od_parity & 1) ^ 1), 0, sizeof(int32_t), st);
+    PGW_REQUIRE(me == hipSuccess, "%s: od_count reset: %s", who, hipGetErrorString(me));
+  }
+  const double pv_ob = p->pv.rescale ? (2.0 * std::min(std::max(-s->pv_pmax, p->pv.obs_low), p->pv.obs_high)
+                                        - (p->pv.obs_low + p->pv.obs_high)) / (p->pv.obs_high - p->pv.obs_low)
+                                     : -s->pv_pmax;
+  rc = launch_coord_agents(*p, *s, n, b, pv_ob, std_layout, st);
+  if (rc) return rc;
+  CoordPFArgs c = {};
+  c.n_agents = p->n_agents;
+  c.coordinated = p->coordinated;
+  c.vv_row = p->vv_row;
+  for (int a = 0; a < p->n_agents; ++a) c.agent_ctrl[a] = p->agent_ctrl[a];
+  c.vv_lo = p->vv_lo;
+  c.vv_hi = p->vv_hi;
+  c.vv_penalty = p->vv_penalty;
+  launch_timed(PGW_T_COORD_PF, k_coord_pf_od_h1<14, Bufs>, dim3(grid_for(n)), dim3(kBlock), st, c,
+               make_pf_args(*pf, *pft), make_od_args(*pft->od, pf->max_iter), make_h1_args(*pf, *h), *pft, n, b);
+  return check_launch("k_coord_pf_od_h1");
 }
 
 extern "C" {
@@ -4192,6 +4323,18 @@ int32_t pgw_pf_solve_h1_f32(const pgw_pf_params* p, const pgw_pf_tables* t, cons
                             const float* ctrl_p, const float* ctrl_q, float* v_out, int32_t* iters,
                             void* stream) {
   return pf_solve_h1(p, t, h, n, ctrl_p, ctrl_q, v_out, iters, stream);
+}
+
+int32_t pgw_coord_step_h1(const pgw_coord_params* p, const pgw_pf_params* pf, const pgw_pf_tables* pft,
+                          const pgw_pf_h1* h, const pgw_coord_step_info* s, int64_t n, pgw_coord_buffers b,
+                          void* stream) {
+  return coord_step_h1(p, pf, pft, h, s, n, b, stream);
+}
+
+int32_t pgw_coord_step_h1_f32(const pgw_coord_params* p, const pgw_pf_params* pf, const pgw_pf_tables* pft,
+                              const pgw_pf_h1* h, const pgw_coord_step_info* s, int64_t n,
+                              pgw_coord_buffers_f32 b, void* stream) {
+  return coord_step_h1(p, pf, pft, h, s, n, b, stream);
 }
 
 int32_t pgw_pf_solve(const pgw_pf_params* p, const pgw_pf_tables* t, int64_t n,

@@ -153,9 +153,22 @@ def h1_hour_reduction(W2, u0, dD):
 
 def h1_hour_rows(G, V0, dD, Wh, u0h):
     """Rows V0 + G J of the file model (G [R, M], V0 [R]) as the hour's V0_h +
-    G_h J': G_h = G (I + dD W_h), V0_h = V0 + G dD u0_h.  Pure NumPy."""
-    GD = G * dD[None, :]
-    return G + GD @ Wh, V0 + GD @ u0h
+    G_h J': G_h = G (I + dD W_h), V0_h = V0 + G dD u0_h.  Pure NumPy.
+    The two products are summed term by term in index order on real and
+    imaginary parts, so a row's bits do not depend on which other rows are
+    asked for: BLAS rounds a row by the product's shape, and a solver that
+    outputs one node (the fused C4 step) owes that node the bits of a solver
+    that outputs them all (the generic path, the on-demand env.voltages)."""
+    B = np.concatenate([Wh, u0h[:, None]], axis=1)           # [M, M + 1]: G dD W_h and G dD u0_h at once
+    ar = G.real * dD.real[None, :] - G.imag * dD.imag[None, :]
+    ai = G.real * dD.imag[None, :] + G.imag * dD.real[None, :]
+    br, bi = B.real, B.imag
+    re, im = np.zeros((G.shape[0], B.shape[1])), np.zeros((G.shape[0], B.shape[1]))
+    for k in range(B.shape[0]):
+        re += ar[:, k, None] * br[None, k] - ai[:, k, None] * bi[None, k]
+        im += ar[:, k, None] * bi[None, k] + ai[:, k, None] * br[None, k]
+    P = re + 1j * im
+    return G + P[:, :-1], V0 + P[:, -1]
 
 
 def h1_hour_tables(W2, u0, y0, base_kw, base_kvar, nph, G_out, V0_out, G_chk, V0_chk, elem):

@@ -322,7 +322,7 @@ class StepGraph:
 
 class CoordStepGraph:
     """Captured steps of the fused multi-agent step (MultiAgentEnv fused path,
-    pgw_coord_step / _f32 / _general): `steps` consecutive steps per graph,
+    pgw_coord_step / _f32 / _general / _h1): `steps` consecutive steps per graph,
     captured once per episode position (and step parity of the fused step's
     list counters) on first use, each step's launches holding that step's
     constants as the eager step builds them (_step_entry: exogenous rows, PV
@@ -395,7 +395,10 @@ class CoordStepGraph:
         def launch():
             st = _lib.stream_ptr(env.device)
             for (info, pfp, pft, _), b in launches:
-                _lib.check(fn(F["params"], pfp, pft, info, n, b, st))
+                if F["h1"]:           # yprim="step": the hour's pgw_pf_h1 with its tables
+                    _lib.check(fn(F["params"], pfp, pft, pft._h1, info, n, b, st))
+                else:
+                    _lib.check(fn(F["params"], pfp, pft, info, n, b, st))
         g = _capture(env.device, launch)
         self._pos[key] = (g, launches, acts)          # (the launches' structs live as long as the graph)
         return g

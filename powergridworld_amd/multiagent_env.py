@@ -411,7 +411,10 @@ class MultiAgentEnv(Env):
             return "RegControl (the control loop runs in OpenDSSSolver.calculate_power_flow)"
         if getattr(self.pf_solver, "snap_start", "direct") != "direct":
             return "snap_start='previous' (each env's solve starts from its own previous solution)"
-        if getattr(self.pf_solver, "yprim", "dss_file") != "dss_file":
+        if getattr(self.pf_solver, "yprim", "dss_file") != "dss_file" and \
+                not self.pf_solver.h1_fast_serves(sorted(set(self.agent_name_bus_map.values()))):
+            # step_kernel="fast" with the agents on one load of one phase element
+            # takes pgw_coord_step_h1 (the agents' kernel, then k_coord_pf_od_h1)
             return "yprim='step' (every solve's Y holds its own loads' admittances)"
         if getattr(self.pf_solver, "multi_bus", "general") == "fast" and self.pf_solver._od_fast and \
                 len(set(b for b in self.agent_name_bus_map.values() if b in self.pf_solver.load_bus_name)) > 1:
@@ -644,6 +647,11 @@ class MultiAgentEnv(Env):
         F["Mat"] = _lib.Matf if f32 else _lib.Mat
         F["kernel"] = "pgw_coord_step_f32" if f32 else (
             "pgw_coord_step_general" if self.pf_solver.general else "pgw_coord_step")
+        # yprim="step" on the fast kernel: the H1 entries, which also take the
+        # hour's pgw_pf_h1 (it lives on the step-cache entry's tables, pft._h1)
+        F["h1"] = bool(getattr(self.pf_solver, "_h1_fast", False))
+        if F["h1"]:
+            F["kernel"] = "pgw_coord_step_h1_f32" if f32 else "pgw_coord_step_h1"
         obs = F["obs"]
         bufs.obs = F["Mat"](obs.data_ptr(), 1, obs.stride(1))
         bufs.obs_stride_agent = obs.stride(0)
@@ -673,6 +681,7 @@ class MultiAgentEnv(Env):
             F["meta"]["voltage_violation"] = F["vv"]
         F["meta"]["oob_actions"] = self.oob_count
         self._fused = F
+        assert not (F["h1"] and self._one_launch_ok()), "the H1 step has no response table"
         if self._one_launch_ok():
             self.set_pf_list(True)
 
@@ -1013,8 +1022,11 @@ class MultiAgentEnv(Env):
             bufs.v_out, bufs.agent_power = H["v"][s_].data_ptr(), H["p"][s_].data_ptr()
         if F.get("od_on"):
             bufs.od_parity ^= 1
-        rc = getattr(_lib.lib(), F["kernel"])(F["params"], pfp, pft, info,
-                                              self.num_envs, bufs, _lib.stream_ptr(self.device))
+        fn, st = getattr(_lib.lib(), F["kernel"]), _lib.stream_ptr(self.device)
+        if F["h1"]:
+            rc = fn(F["params"], pfp, pft, pft._h1, info, self.num_envs, bufs, st)
+        else:
+            rc = fn(F["params"], pfp, pft, info, self.num_envs, bufs, st)
         if rc:
             _lib.check(rc)
         return self._fused_post(H, s_ if H is not None else None)

@@ -7,7 +7,8 @@ at 65,536 envs, one process, the two alternated in every round:
   * the heterogeneous scenario's step (tools/bench_configs.py HETYG / HETYF:
     the generic agents and the general kernel against the fused multi-agent
     step and pgw_pf_solve_h1), host clock around synchronised regions;
-  * the C4 scenario's generic step (the one-launch step refuses yprim="step")
+  * the C4 scenario's generic step (fused=False: with step_kernel="fast" the
+    default route is the fused pgw_coord_step_h1, tools/gpu/ab_coord_h1.py)
     with the solve on either kernel.
 Usage: python tools/gpu/ab_h1.py [rounds] [reps] [steps]"""
 import os
@@ -122,7 +123,7 @@ envs = []
 for mode in MODES:
     cfg = make_c4_config()
     cfg["pf_config"]["config"].update(yprim="step", step_kernel=mode)
-    envs.append(CoordinatedMultiBuildingControlEnv(**cfg, num_envs=n, device=dev))
+    envs.append(CoordinatedMultiBuildingControlEnv(**cfg, num_envs=n, device=dev, fused=False))
     assert envs[-1]._fused is None and envs[-1]._ma is None
 ab("C4 generic step", envs, max(steps // 4, 24))
 for e, mode in zip(envs, MODES):
