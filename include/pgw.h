@@ -994,6 +994,23 @@ int32_t pgw_coord_step(const pgw_coord_params* p, const pgw_pf_params* pf,
                        const pgw_pf_tables* pft, const pgw_coord_step_info* s, int64_t n,
                        pgw_coord_buffers b, void* stream);
 
+/* pgw_coord_step told which observation rows the buffer already holds.  Bit j
+ * of obs_rows_held set: observation slot j of EVERY agent already holds, for
+ * all n envs, the value this step would store there (the caller's promise: the
+ * same source scalar bit for bit as at the last step that wrote b.obs, and no
+ * other write to those rows since).  Only the slots of the standard C4 layout
+ * that depend on neither env nor agent can be held: 10, 11 (comfort_lb / _ub
+ * of ex_next), 12 (ex_next.T_oa), 14 (ex_next.time_of_day) and 15 (the PV
+ * observation, from pv_pmax).  PGW_ERR_ARG before any launch for any other
+ * bit, and for a non-zero mask with another agent layout.  The one-launch step
+ * (k_coord_step_od) neither forms nor stores a held row: 8 B x n_agents x n
+ * less written per row.  Every other route through the entry (the two-kernel
+ * step, PGW_STEP_LIST=1) ignores the mask and stores all rows, which is always
+ * correct.  obs_rows_held = 0 is pgw_coord_step. */
+int32_t pgw_coord_step_rows(const pgw_coord_params* p, const pgw_pf_params* pf,
+                            const pgw_pf_tables* pft, const pgw_coord_step_info* s, int64_t n,
+                            pgw_coord_buffers b, void* stream, uint32_t obs_rows_held);
+
 /* fp32-storage variant: every per-env buffer fp32, arithmetic in fp64 (the
  * power flow included: the agent powers are widened and summed in fp64, the
  * solve is the fp64 one).  Standard C4 agent layout only ([building, pv,

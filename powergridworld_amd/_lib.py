@@ -383,6 +383,8 @@ _SIGS = {
     "pgw_pf_reduce": (i32, [i32, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp]),
     "pgw_coord_step": (i32, [P(CoordParams), P(PFParams), P(PFTables), P(CoordStepInfo), i64,
                              CoordBuffers, vp]),
+    "pgw_coord_step_rows": (i32, [P(CoordParams), P(PFParams), P(PFTables), P(CoordStepInfo), i64,
+                                  CoordBuffers, vp, C.c_uint32]),
     "pgw_coord_step_f32": (i32, [P(CoordParams), P(PFParams), P(PFTables), P(CoordStepInfo), i64,
                                  CoordBuffersF32, vp]),
     "pgw_coord_step_general": (i32, [P(CoordParams), P(PFGParams), P(PFGTables), P(CoordStepInfo), i64,

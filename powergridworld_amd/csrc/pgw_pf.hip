@@ -776,10 +776,19 @@ enum StdSlot { kSlotX = 0, kSlotSoc = 5, kSlotObs = 6, kSlotPower = 23, kSlotRew
 // in their order; only independent chains change places, so the outputs are
 // the same bits.  HALF 0 (every other kernel) is the one-call order and
 // compiles to what it compiled to before the halves existed.
-template <int E, int HALF = 0, class In, class Store>
+// ROWS (k_coord_step_od, pgw_coord_step_rows): `held` bit j set = observation
+// slot j already holds this step's value for every env, so its arithmetic and
+// its store are skipped behind a scalar branch.  Only the env-uniform slots
+// (kObsRowsUniform) can be held; they are taken out of the unrolled loop and
+// tested after it, so the per-env slots keep the code they had (a test inside
+// the loop is the hazard of pgw_common.h, bld_std_step's note).  ROWS = false
+// keeps the loop as it was, text and order: the other kernels' instructions
+// do not change (profiles/r16/step_od_resource_usage.txt).
+constexpr uint32_t kObsRowsUniform = 1u << 10 | 1u << 11 | 1u << 12 | 1u << 14 | 1u << 15;
+template <int E, int HALF = 0, bool ROWS = false, class In, class Store>
 __device__ __forceinline__ void std_agent_compute(const pgw_coord_params& p, const StdDerived& dv,
                                                   const pgw_coord_step_info& s, double pv_ob,
-                                                  In (&in)[E], Store&& store) {
+                                                  In (&in)[E], Store&& store, uint32_t held = 0) {
   const pgw_building_params& B = p.bld;
   double T[E][5], v[E];
   double pc[E], rp_pv[E], power[E];
@@ -852,22 +861,50 @@ __device__ __forceinline__ void std_agent_compute(const pgw_coord_params& p, con
                                exact_div(-pc[q], 12.0, 1.0 / 12.0));
   }
   const double lb = s.ex_next.comfort_lb, ub = s.ex_next.comfort_ub;
+  if constexpr (!ROWS) {
 #pragma unroll
-  for (int j = 0; j < 15; ++j) {
+    for (int j = 0; j < 15; ++j) {
 #pragma unroll
-    for (int q = 0; q < E; ++q) {
-      const double o = j < 5 ? T[q][j] - ub : j < 10 ? lb - T[q][j - 5] : j == 10 ? lb
-                     : j == 11 ? ub : j == 12 ? s.ex_next.T_oa : j == 13 ? pc[q] : s.ex_next.time_of_day;
-      double c = clip_fast(o, B.obs_low[j], B.obs_high[j]);
-      if (B.rescale) c = exact_div(2.0 * c - dv.obs_sum[j], dv.obs_rng[j], dv.obs_rcp[j]);
-      v[q] = c;
+      for (int q = 0; q < E; ++q) {
+        const double o = j < 5 ? T[q][j] - ub : j < 10 ? lb - T[q][j - 5] : j == 10 ? lb
+                       : j == 11 ? ub : j == 12 ? s.ex_next.T_oa : j == 13 ? pc[q] : s.ex_next.time_of_day;
+        double c = clip_fast(o, B.obs_low[j], B.obs_high[j]);
+        if (B.rescale) c = exact_div(2.0 * c - dv.obs_sum[j], dv.obs_rng[j], dv.obs_rcp[j]);
+        v[q] = c;
+      }
+      store(kSlotObs + j, v);
     }
-    store(kSlotObs + j, v);
-  }
-  // ---- pv (obs is env-independent: computed once on the host)
+    // ---- pv (obs is env-independent: computed once on the host)
 #pragma unroll
-  for (int q = 0; q < E; ++q) v[q] = pv_ob;
-  store(kSlotObs + 15, v);
+    for (int q = 0; q < E; ++q) v[q] = pv_ob;
+    store(kSlotObs + 15, v);
+  } else {
+    // the same rows, the per-env ones first, then each env-uniform one unless held
+    auto obs_row = [&](int j) {
+#pragma unroll
+      for (int q = 0; q < E; ++q) {
+        const double o = j < 5 ? T[q][j] - ub : j < 10 ? lb - T[q][j - 5] : j == 10 ? lb
+                       : j == 11 ? ub : j == 12 ? s.ex_next.T_oa : j == 13 ? pc[q] : s.ex_next.time_of_day;
+        double c = clip_fast(o, B.obs_low[j], B.obs_high[j]);
+        if (B.rescale) c = exact_div(2.0 * c - dv.obs_sum[j], dv.obs_rng[j], dv.obs_rcp[j]);
+        v[q] = c;
+      }
+      store(kSlotObs + j, v);
+    };
+#pragma unroll
+    for (int j = 0; j < 15; ++j) {
+      if (!(kObsRowsUniform >> j & 1)) obs_row(j);
+    }
+#pragma unroll
+    for (int j = 0; j < 15; ++j) {
+      if ((kObsRowsUniform >> j & 1) && !(held >> j & 1)) obs_row(j);
+    }
+    if (!(held >> 15 & 1)) {
+#pragma unroll
+      for (int q = 0; q < E; ++q) v[q] = pv_ob;
+      store(kSlotObs + 15, v);
+    }
+  }
   if constexpr (!EARLY) {
 #pragma unroll
     for (int q = 0; q < E; ++q) rp_pv[q] = pv_real_power(p.pv, in[q].av[6], s.pv_pmax);
@@ -2422,6 +2459,10 @@ __device__ int od_wave_solve(const ODWaveArgs& z_, const ODWaveShared& sh_, doub
 // headline shape 4 blocks = 24 waves per CU, 6 per SIMD, one round;
 // profiles/r08/step_od_resource_usage.txt; at 6 the round-6 kernel ran 0.3 us
 // slower, profiles/r06/ab_one_launch_step.txt.)
+// held (pgw_coord_step_rows, 0 = pgw_coord_step): the env-uniform observation
+// rows the buffer already holds; an agent wave of the INL form skips them
+// behind scalar branches (std_agent_compute's ROWS), 8 B x n_agents per env
+// and row less written.
 // (the step's parameters and the wave solve's constants: one first argument,
 // read in place from the kernarg segment)
 struct StepOdArgs {
@@ -2431,7 +2472,8 @@ struct StepOdArgs {
 template <bool WT, bool INL>
 __global__ void __launch_bounds__(64 * (PGW_MAX_AGENTS + 1)) __attribute__((amdgpu_waves_per_eu(7))) k_coord_step_od(StepOdArgs A_, pgw_coord_step_info s,
                                                                        int64_t n, pgw_coord_buffers b, double pv_ob,
-                                                                       StdDerived dv, CoordPFArgs c, ODVLook o) {
+                                                                       StdDerived dv, CoordPFArgs c, ODVLook o,
+                                                                       uint32_t held) {
   auto put = [](auto* q, auto v) {
     if constexpr (WT) st_wt(q, v);
     else *q = v;
@@ -2475,7 +2517,11 @@ __global__ void __launch_bounds__(64 * (PGW_MAX_AGENTS + 1)) __attribute__((amdg
     // the building step, the observations and their stores
     if (valid) {
       double* op = b.obs.ptr + a * b.obs_stride_agent + e * b.obs.s_env;
-      std_agent_compute<1, 2>(p, dv, s, pv_ob, in, [&](int slot, const double (&v)[1]) {
+      // (held: wave-uniform, a kernel argument -- the rows the buffer already
+      // holds are neither formed nor stored.  The list form, PGW_STEP_LIST=1,
+      // takes the argument and stores every row: with the branches its build
+      // reserved a 68 B private segment, profiles/r16/step_od_resource_usage.txt)
+      std_agent_compute<1, 2, INL>(p, dv, s, pv_ob, in, [&](int slot, const double (&v)[1]) {
         if (slot < kSlotSoc) put(xp + slot * n, v[0]);
         else if (slot == kSlotSoc) put(socp, v[0]);
         else if (slot < kSlotPower) {
@@ -2484,7 +2530,7 @@ __global__ void __launch_bounds__(64 * (PGW_MAX_AGENTS + 1)) __attribute__((amdg
         } else {
           rw = v[0];
         }
-      });
+      }, held);
     }
     __syncthreads();
     if (!valid) return;
@@ -3842,13 +3888,20 @@ static int32_t check_coord(const char* who, const pgw_coord_params* p, const pgw
 // epilogue, on one stream.
 template <class Bufs>
 static int32_t coord_step(const pgw_coord_params* p, const pgw_pf_params* pf, const pgw_pf_tables* pft,
-                          const pgw_coord_step_info* s, int64_t n, const Bufs& b, void* stream) {
+                          const pgw_coord_step_info* s, int64_t n, const Bufs& b, void* stream,
+                          uint32_t held = 0) {
   constexpr bool kF32 = std::is_same<Bufs, pgw_coord_buffers_f32>::value;
   const int32_t rc_args = check_coord("pgw_coord_step", p, pf, pft, s, n, b);
   if (rc_args) return rc_args;
+  // pgw_coord_step_rows: only the env-uniform slots of the standard agent can be held
+  PGW_REQUIRE((held & ~kObsRowsUniform) == 0,
+              "pgw_coord_step_rows: obs_rows_held 0x%x names a slot that is not env-uniform (10, 11, 12, 14, 15)",
+              (unsigned)held);
+  const bool std_layout = coord_is_std(*p);
+  PGW_REQUIRE(std_layout || !held,
+              "pgw_coord_step_rows: held rows need the standard C4 agent layout (building/pv/storage at 0/6/7)");
   if (n == 0) return PGW_OK;
   hipStream_t st = (hipStream_t)stream;
-  const bool std_layout = coord_is_std(*p);
   PGW_REQUIRE(std_layout || !kF32,
               "pgw_coord_step_f32: needs the standard C4 agent layout (building/pv/storage at 0/6/7)");
   if (pft->od) {
@@ -3884,18 +3937,18 @@ static int32_t coord_step(const pgw_coord_params* p, const pgw_pf_params* pf, co
         if (!g_step_list) {                         // the one-launch step
           if (g_step_wt)
             launch_timed(PGW_T_COORD_AGENTS, k_coord_step_od<true, true>, grid, block, st, sa, *s, n, b, pv_ob,
-                         make_std_derived(*p), c, lk);
+                         make_std_derived(*p), c, lk, held);
           else
             launch_timed(PGW_T_COORD_AGENTS, k_coord_step_od<false, true>, grid, block, st, sa, *s, n, b, pv_ob,
-                         make_std_derived(*p), c, lk);
+                         make_std_derived(*p), c, lk, held);
           return check_launch("k_coord_step_od");
         }
         if (g_step_wt)
           launch_timed(PGW_T_COORD_AGENTS, k_coord_step_od<true, false>, grid, block, st, sa, *s, n, b, pv_ob,
-                       make_std_derived(*p), c, lk);
+                       make_std_derived(*p), c, lk, held);
         else
           launch_timed(PGW_T_COORD_AGENTS, k_coord_step_od<false, false>, grid, block, st, sa, *s, n, b, pv_ob,
-                       make_std_derived(*p), c, lk);
+                       make_std_derived(*p), c, lk, held);
         int32_t rc = check_launch("k_coord_step_od");
         if (rc) return rc;
         if (g_step_nop) hipLaunchKernelGGL(k_step_nop, dim3(1), dim3(64), 0, st, (int*)nullptr);
@@ -4352,6 +4405,12 @@ int32_t pgw_pf_solve_f32(const pgw_pf_params* p, const pgw_pf_tables* t, int64_t
 int32_t pgw_coord_step(const pgw_coord_params* p, const pgw_pf_params* pf, const pgw_pf_tables* pft,
                        const pgw_coord_step_info* s, int64_t n, pgw_coord_buffers b, void* stream) {
   return coord_step(p, pf, pft, s, n, b, stream);
+}
+
+int32_t pgw_coord_step_rows(const pgw_coord_params* p, const pgw_pf_params* pf, const pgw_pf_tables* pft,
+                            const pgw_coord_step_info* s, int64_t n, pgw_coord_buffers b, void* stream,
+                            uint32_t obs_rows_held) {
+  return coord_step(p, pf, pft, s, n, b, stream, obs_rows_held);
 }
 
 int32_t pgw_coord_step_f32(const pgw_coord_params* p, const pgw_pf_params* pf,

@@ -391,6 +391,9 @@ class CoordStepGraph:
             launches.append((ent, self._step_bufs(acts[i], (parity + 1 + i) & 1)))
         fn = getattr(_lib.lib(), F["kernel"])
         n = env.num_envs
+        # (captured with every observation row stored: pgw_coord_step, mask 0;
+        # the env forgets what its buffer holds at the capture and at every call)
+        env._obs_rows_forget()
 
         def launch():
             st = _lib.stream_ptr(env.device)
@@ -420,6 +423,7 @@ class CoordStepGraph:
             raise IndexError("capture_step: steps %d..%d run past the episode's last step %d (step eagerly "
                              "or reset)" % (k + 1, k + self.steps, last))
         parity = F["bufs"].od_parity if F.get("od_on") else 0
+        env._obs_rows_forget()
         self._graph_at(k, parity).launch(_lib.stream_ptr(env.device))
         for _ in range(self.steps):
             out = env._advance_fused()

@@ -20,6 +20,10 @@ from collections.abc import Mapping
 from typing import Dict, Tuple, Union
 
 import ctypes as C
+import itertools
+import os
+import struct
+
 import numpy as np
 import pandas as pd
 import torch
@@ -36,6 +40,36 @@ except ImportError:
     logger.warning("rllib MultiAgentEnv not found, using generic object class")
 
 _KIND_ID = {"building": 0, "pv": 1, "storage": 2}
+
+# pgw_coord_step_rows: the observation slots of the standard C4 agent that
+# depend on neither env nor agent, in the order of obs_rows_key's scalars
+OBS_ROWS_UNIFORM = (10, 11, 12, 14, 15)
+_OBS_ROWS_ALL = sum(1 << j for j in OBS_ROWS_UNIFORM)
+_POPCOUNT = {m: bin(m).count("1") for m in
+             (sum(1 << j for j, on in zip(OBS_ROWS_UNIFORM, bits) if on)
+              for bits in itertools.product((0, 1), repeat=len(OBS_ROWS_UNIFORM)))}
+
+
+def obs_rows_key(comfort_lb, comfort_ub, T_oa, time_of_day, pv_pmax):
+    """The five source scalars of the env-uniform observation rows by BIT
+    PATTERN (five int64): -0.0 stays distinct from 0.0, and a NaN equals only
+    the NaN of the same bits."""
+    return struct.unpack("<5q", struct.pack("<5d", comfort_lb, comfort_ub, T_oa, time_of_day, pv_pmax))
+
+
+def obs_rows_held(held_key, key):
+    """obs_rows_held of pgw_coord_step_rows: bit j set where the key of the last
+    step that wrote the observation buffer (None: unknown, nothing held) and
+    this step's key agree on slot j's scalar."""
+    if held_key is None:
+        return 0
+    if held_key == key:                  # (the usual night step: one tuple compare)
+        return _OBS_ROWS_ALL
+    mask = 0
+    for j, a, b in zip(OBS_ROWS_UNIFORM, held_key, key):
+        if a == b:
+            mask |= 1 << j
+    return mask
 
 
 def resolve_pf_class(cls):
@@ -56,8 +90,14 @@ class MultiAgentEnv(Env):
     def __init__(self, common_config: dict = {}, pf_config: dict = {}, agents: list = None,
                  max_episode_steps: int = None, rescale_spaces: bool = True, num_envs: int = 1,
                  device=None, fused: Union[bool, str] = "auto", record_history: bool = False,
-                 dtype=None, history_capacity: int = None, **kwargs):
+                 dtype=None, history_capacity: int = None, obs_row_skip: bool = True, **kwargs):
         self.common_config = common_config
+        # fused fp64 step: an env-uniform observation row is stored only when its
+        # value changes (pgw_coord_step_rows; see step()).  PGW_OBS_ROW_SKIP=0
+        # turns it off for every env built while it is set (A/B runs).  In a dict:
+        # neither the switch nor the counter nor the held key is checkpointed state.
+        self._obs_rows = {"on": bool(obs_row_skip) and os.environ.get("PGW_OBS_ROW_SKIP", "1") != "0",
+                          "skipped": 0, "key": None}
         self.rescale_spaces = rescale_spaces
         assert len(agents) > 0, "need at least one agent!"
         self.num_envs = int(num_envs)
@@ -195,8 +235,30 @@ class MultiAgentEnv(Env):
             self._end_step = next((i for i, t in enumerate(times) if t >= self.end_time), n + 10 ** 9)
         return times[step]
 
+    @property
+    def obs_row_skip(self):
+        """Fused fp64 step: leave an env-uniform observation row in place while
+        its value repeats (False: every step stores all rows)."""
+        return self._obs_rows["on"]
+
+    @obs_row_skip.setter
+    def obs_row_skip(self, on):
+        self._obs_rows["on"] = bool(on)
+        self._obs_rows["key"] = None
+
+    @property
+    def obs_rows_skipped(self):
+        """Observation rows (per agent) the fused steps left in place so far."""
+        return self._obs_rows["skipped"]
+
+    def _obs_rows_forget(self):
+        """Something other than the eager fused step wrote (or may have written)
+        the observation buffer: the next step stores all its rows."""
+        self._obs_rows["key"] = None
+
     def reset(self) -> Dict[str, any]:
         """multiagent_env.py:125-140"""
+        self._obs_rows_forget()          # the components' resets write their observations
         self.episode_step = 0
         self._resets = self.__dict__.get("_resets", 0) + 1
         oob_poll(self.oob_count)
@@ -244,7 +306,18 @@ class MultiAgentEnv(Env):
     def step(self, action) -> Tuple[dict, dict, dict, dict]:
         """multiagent_env.py:151-212.  ``action`` is the reference's
         {agent: {component: [N, d]}} dict, or -- fused path -- one packed tensor
-        [n_agents, N, act_dim] (any strides; zero-copy)."""
+        [n_agents, N, act_dim] (any strides; zero-copy).
+
+        Fused path: the returned observations (and ``packed_obs()``) are views
+        of persistent buffers that the next step overwrites in place.  The
+        fp64 one-launch step rewrites an env-uniform observation row (the
+        building's comfort bounds, next outdoor temperature and time of day,
+        the PV observation) only when its value changes from the step before;
+        a caller that edits the returned tensors in place must construct the
+        env with ``obs_row_skip=False`` (or set ``env.obs_row_skip = False``),
+        which stores all rows every step.  ``reset()``, ``load_state_dict()``,
+        ``load_component_state()`` and captured steps make the next step store
+        all rows."""
         self.episode_step += 1
         self.time = self._time_at(self.episode_step)
         self._at_reset = False
@@ -494,6 +567,7 @@ class MultiAgentEnv(Env):
         up: fp32 -> components (x_k persists across resets, as in the
         reference); down: components -> fp32 after their reset."""
         F = self._fused
+        self._obs_rows_forget()
         for ai, agent in enumerate(self.agents):
             bld, pv, bat = agent.envs
             if up:
@@ -557,6 +631,7 @@ class MultiAgentEnv(Env):
         """fp32 fused path: re-read the component envs' state and observations
         into the fp32 step buffers, after a component was reset directly (e.g.
         ``agent.env_dict["storage"].reset(init_storage=...)``).  No-op otherwise."""
+        self._obs_rows_forget()
         if self._fused is not None and self.dtype != torch.float64:
             self._f32_sync(up=False)
         return self.packed_obs() if self._fused is not None else None
@@ -680,10 +755,28 @@ class MultiAgentEnv(Env):
         if self.fused_reward_transform == "coordinated":
             F["meta"]["voltage_violation"] = F["vv"]
         F["meta"]["oob_actions"] = self.oob_count
+        # the entry that is told which rows the buffer holds: the fp64 step of
+        # the standard agent (pgw_coord_step_rows refuses held rows otherwise)
+        F["rows"] = F["kernel"] == "pgw_coord_step" and self._std_layout(p)
+        self._obs_rows_forget()
         self._fused = F
         assert not (F["h1"] and self._one_launch_ok()), "the H1 step has no response table"
         if self._one_launch_ok():
             self.set_pf_list(True)
+
+    @staticmethod
+    def _std_layout(p):
+        """libpgw's coord_is_std: the standard C4 agent ([building, pv, storage]
+        at actions 0/6/7, observations 0/15/16, the reference's 5-zone model
+        structure and the default building observations)."""
+        sel = [[0, 7, 6, 1]] * 2 + [[0, 7, 5, 1]] * 3
+        nbr = [[j for j in range(5) if j != z] for z in range(5)]
+        return (p.n_comp == 3 and list(p.comp_order) == [0, 1, 2] and
+                (p.act_bld, p.act_pv, p.act_bat, p.act_dim) == (0, 6, 7, 8) and
+                (p.obs_bld, p.obs_pv, p.obs_bat, p.obs_dim) == (0, 15, 16, 17) and
+                not p.pv.grid_aware and p.bld.n_obs == 15 and
+                [list(r) for r in p.bld.sel] == sel and [list(r) for r in p.bld.nbr] == nbr and
+                list(p.bld.obs_var)[:15] == list(range(5, 20)))
 
     # ================================================================ fused multi-agent path
     def _ma_fusable(self):
@@ -951,6 +1044,7 @@ class MultiAgentEnv(Env):
         F = self._fused
         if F is None:
             return
+        self._obs_rows_forget()
         b = F["bufs"]
         if enabled:
             if "od_list" not in F:
@@ -1022,7 +1116,23 @@ class MultiAgentEnv(Env):
             bufs.v_out, bufs.agent_power = H["v"][s_].data_ptr(), H["p"][s_].data_ptr()
         if F.get("od_on"):
             bufs.od_parity ^= 1
-        fn, st = getattr(_lib.lib(), F["kernel"]), _lib.stream_ptr(self.device)
+        st = _lib.stream_ptr(self.device)
+        if F["rows"]:
+            # the rows whose source scalar repeats, bit for bit, that of the last
+            # step that wrote the buffer; only the one-launch step skips them
+            R = self._obs_rows
+            rkey, held_key = info._rows_key, R["key"]
+            held = obs_rows_held(held_key, rkey) if R["on"] and F.get("od_on") else 0
+            R["key"] = None                          # (nothing held if the launch fails)
+            rc = _lib.lib().pgw_coord_step_rows(F["params"], pfp, pft, info, self.num_envs, bufs, st, held)
+            if rc:
+                _lib.check(rc)
+            R["key"] = rkey
+            if held:
+                R["skipped"] += _POPCOUNT[held]
+            return self._fused_post(H, s_ if H is not None else None)
+        self._obs_rows["key"] = None
+        fn = getattr(_lib.lib(), F["kernel"])
         if F["h1"]:
             rc = fn(F["params"], pfp, pft, pft._h1, info, self.num_envs, bufs, st)
         else:
@@ -1078,6 +1188,7 @@ class MultiAgentEnv(Env):
         self._at_reset = False
         self.obs_dict = {}
         F = self._fused
+        self._obs_rows_forget()          # a captured step stores all rows, with its own values
         if F.get("od_on"):
             F["bufs"].od_parity ^= 1
         obs, rew, done, meta = self._fused_post(None, None)
@@ -1127,6 +1238,8 @@ class MultiAgentEnv(Env):
             info.ex_t, info.ex_next = bld._exo[t], bld._exo[t + 1]
         if pv is not None:
             info.pv_pmax = float(pv.data[p])
+        exn = info.ex_next       # (read back from the struct: the bits the kernel gets)
+        info._rows_key = obs_rows_key(exn.comfort_lb, exn.comfort_ub, exn.T_oa, exn.time_of_day, info.pv_pmax)
         pfp = solver.step_params(time)
         pft = solver.step_tables(time)
         if len(F["step_cache"]) > 1 << 14:
@@ -1167,6 +1280,7 @@ class MultiAgentEnv(Env):
         """Restore a state_dict() of an env of the same configuration (in place),
         then point the {node: voltage} mapping at the restored step's outputs."""
         from powergridworld_amd.checkpoint import load_state_dict
+        self._obs_rows_forget()          # the observation buffer is the checkpoint's
         load_state_dict(self, sd, strict)
         self._rearm_voltages()
         return self
