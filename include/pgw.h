@@ -567,6 +567,46 @@ int32_t pgw_pf_solve_h1_f32(const pgw_pf_params* p, const pgw_pf_tables* t, cons
                             const float* ctrl_p, const float* ctrl_q, float* v_out, int32_t* iters,
                             void* stream);
 
+/* OpenDSS's snap solve in the reading where every solve continues from the
+ * env's previous solution (OpenDSSSolver snap_start="previous",
+ * start_kernel="fast"; oracle/pf_oracle.py Feeder.snap_opendss chained through
+ * V_start) on the fast one-lane-per-env kernel, for feeders of the fast shape
+ * (m = 14 constant-PQ elements, one voltage band) with at most one
+ * controllable slot (any number of phase elements on it).  The map is
+ * pgw_pf_od's with Y the DSS file's (H2) -- t->block, the output rows, t->od's
+ * y0', elem_scale, check rows and bound constants exactly as pgw_pf_solve reads
+ * them -- except for the start.  Per env:
+ *   start        u = the env's column of U;
+ *   iteration 1  J' = I'(u) (pgw_pf_od's compensation currents), u_1 = u0 + W'' J':
+ *                a full iteration, no first-iteration table, never tested
+ *                (min_iter >= 2);
+ *   iteration k  pgw_pf_od's, with its stopping rule and outputs;
+ *   end          the env's column of U <- the newest iterate u_k (what the
+ *                general kernel's U_out holds), also where max_iter stopped it.
+ * Every env is solved.
+ * U: [2 m][n] fp64 on the device, env-minor -- row 2k holds Re u_k of every
+ * env, row 2k + 1 Im u_k, element voltages in the block's per-unit (u = U /
+ * vbase); fp64 in the fp32-storage variants too.  It is read and written in
+ * place (each env its own column), and must have been written by
+ * pgw_pf_prev_reset or by an earlier pgw_pf_solve_prev / pgw_coord_step_prev
+ * over the same n: there is no start flag, "the first solve starts from the
+ * direct solution" means U holds it. */
+/* The block's direct solution u0 into every env's column of U.  PGW_ERR_ARG
+ * for a shape other than m = 14, a NULL block or U. */
+int32_t pgw_pf_prev_reset(const pgw_pf_params* p, const pgw_pf_tables* t, double* U, int64_t n, void* stream);
+/* pgw_pf_solve's arguments and outputs, plus U.  PGW_ERR_ARG, before any
+ * launch, for: t->od NULL; a shape other than m = 14 with one voltage band;
+ * n_ctrl > 1; od min_iter < 2; U_init, U_out or load_scale set; od resp /
+ * resp_v / resp_q / start set (the result depends on the env's history, so no
+ * table can serve it); U NULL. */
+int32_t pgw_pf_solve_prev(const pgw_pf_params* p, const pgw_pf_tables* t, double* U, int64_t n,
+                          const double* ctrl_p, const double* ctrl_q, double* v_out, int32_t* iters,
+                          void* stream);
+/* fp32-storage variant, as pgw_pf_solve_f32 (U stays fp64). */
+int32_t pgw_pf_solve_prev_f32(const pgw_pf_params* p, const pgw_pf_tables* t, double* U, int64_t n,
+                              const float* ctrl_p, const float* ctrl_q, float* v_out, int32_t* iters,
+                              void* stream);
+
 /* Response-table builder (OpenDSSSolver._od_response): the snap solve of
  * pgw_pf_od at n lanes, lane e at controllable kW P[e] (Q = 0) in hour
  * e / lanes_per_hour (a multiple of 256): hour h uses p_hours[h] (its base
@@ -1078,6 +1118,24 @@ int32_t pgw_coord_step_h1(const pgw_coord_params* p, const pgw_pf_params* pf, co
 int32_t pgw_coord_step_h1_f32(const pgw_coord_params* p, const pgw_pf_params* pf, const pgw_pf_tables* pft,
                               const pgw_pf_h1* h, const pgw_coord_step_info* s, int64_t n,
                               pgw_coord_buffers_f32 b, void* stream);
+
+/* The coordinated step under OpenDSSSolver snap_start="previous",
+ * start_kernel="fast" (pgw_pf_solve_prev's map and state buffer U): two
+ * launches on the stream, the agents' kernel pgw_coord_step picks for the
+ * layout, then k_coord_pf_od_prev, one lane per env -- pgw_coord_step_h1's bus
+ * load (0 + p_0 + p_1 + ... in agent order, Q = 0), outputs and coordinated
+ * reward, around pgw_pf_solve_prev's solve from and into U.  Bit-identical to
+ * the agents' entries, pgw_agent_reduce, pgw_pf_solve_prev and the host's
+ * reward transform.  od_list is not read; od_count, if set, has the next
+ * step's counter zeroed.  PGW_ERR_ARG, before any launch, for everything
+ * pgw_coord_step refuses and everything pgw_pf_solve_prev refuses. */
+int32_t pgw_coord_step_prev(const pgw_coord_params* p, const pgw_pf_params* pf, const pgw_pf_tables* pft,
+                            double* U, const pgw_coord_step_info* s, int64_t n, pgw_coord_buffers b,
+                            void* stream);
+/* fp32-storage variant, as pgw_coord_step_f32 (the solve, the extrema and U fp64). */
+int32_t pgw_coord_step_prev_f32(const pgw_coord_params* p, const pgw_pf_params* pf, const pgw_pf_tables* pft,
+                                double* U, const pgw_coord_step_info* s, int64_t n, pgw_coord_buffers_f32 b,
+                                void* stream);
 
 /* ------------------------------------------------------------------------
  * Fused MultiComponentEnv step (SURVEY 8(b) pgw_mc_agent_step): one agent of

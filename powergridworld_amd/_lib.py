@@ -363,6 +363,10 @@ _SIGS = {
     "pgw_pf_solve_f32": (i32, [P(PFParams), P(PFTables), i64, vp, vp, vp, vp, vp]),
     "pgw_pf_solve_h1": (i32, [P(PFParams), P(PFTables), P(PFH1), i64, vp, vp, vp, vp, vp]),
     "pgw_pf_solve_h1_f32": (i32, [P(PFParams), P(PFTables), P(PFH1), i64, vp, vp, vp, vp, vp]),
+    # snap_start="previous" on the fast kernel: U is the per-env state buffer [2 m][n] fp64
+    "pgw_pf_prev_reset": (i32, [P(PFParams), P(PFTables), vp, i64, vp]),
+    "pgw_pf_solve_prev": (i32, [P(PFParams), P(PFTables), vp, i64, vp, vp, vp, vp, vp]),
+    "pgw_pf_solve_prev_f32": (i32, [P(PFParams), P(PFTables), vp, i64, vp, vp, vp, vp, vp]),
     "pgw_pf_solve_general": (i32, [P(PFGParams), P(PFGTables), i64, vp, vp, vp, vp, vp]),
     "pgw_reg_factor": (i32, [P(RegParams), i64, vp, vp, vp, vp]),
     "pgw_reg_control": (i32, [P(RegParams), i64, vp, vp, vp, vp, vp, vp]),
@@ -393,6 +397,10 @@ _SIGS = {
                                 CoordBuffers, vp]),
     "pgw_coord_step_h1_f32": (i32, [P(CoordParams), P(PFParams), P(PFTables), P(PFH1), P(CoordStepInfo), i64,
                                     CoordBuffersF32, vp]),
+    "pgw_coord_step_prev": (i32, [P(CoordParams), P(PFParams), P(PFTables), vp, P(CoordStepInfo), i64,
+                                  CoordBuffers, vp]),
+    "pgw_coord_step_prev_f32": (i32, [P(CoordParams), P(PFParams), P(PFTables), vp, P(CoordStepInfo), i64,
+                                      CoordBuffersF32, vp]),
     "pgw_hs_reset": (i32, [P(HSParams), P(HSStepInfo), i64, vp, HSBuffers, vp]),
     "pgw_mc_agent_step": (i32, [P(MCStepArgs), i64, vp]),
     "pgw_mc_agent_step_f32": (i32, [P(MCStepArgsF32), i64, vp]),

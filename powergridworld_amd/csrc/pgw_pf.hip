@@ -1524,6 +1524,8 @@ constexpr uint64_t kFnvBasis = 0xcbf29ce484222325ull, kFnvPrime = 0x100000001b3u
 // (od_first_h1); its current law takes y0' = the lane's own s_k, and its
 // correct() adds the env's rank-1 Yeq correction to the matvec's result and to
 // the stored currents -- compile-time branches on SV::kH1 only.
+// PFSolverPrev<M> (k_pf_solve_od_prev, snap_start="previous") runs iteration 1
+// from the env's previous solution (od_first_prev); nothing else differs.
 template <int M, bool SIG = false, class SV = PFSolver<M, true, false>>
 __device__ int od_solve(SV& S, const ODArgs& o, const ODStage<M>& g, bool valid,
                         ODShared<M>& sh, uint64_t* sig = nullptr) {
@@ -3426,6 +3428,239 @@ __global__ void __launch_bounds__(kBlock) k_coord_pf_od_h1(CoordPFArgs c, PFArgs
   }
 }
 
+// ---- snap_start = "previous": every env's solve continues from its last one ---
+// (pgw_pf_solve_prev, include/pgw.h.)  Y stays the DSS file's (H2), so the block,
+// the check rows, their bound constants and the current law are pgw_pf_od's
+// unchanged; only the start differs: the lane's element voltages come from its
+// column of the state buffer U ([2 M][n] fp64, env-minor: row 2k Re u_k, row
+// 2k + 1 Im u_k, the block's units), which the kernel overwrites with the newest
+// iterate at the end.  The start is not affine in (P, Q), so iteration 1 is a
+// full iteration (od_first_prev) and takes no table; from iteration 2 on
+// od_solve runs unchanged (SV::kMulti).  "The first solve starts direct" means U
+// holds u0 (k_pf_prev_reset): there is no start flag, and a captured graph
+// replays the same launch at every step.
+template <int M> struct PFSolverPrev : PFSolver<M, true, false> {
+  static constexpr bool kMulti = true;           // the caller runs iteration 1 (od_first_prev)
+};
+
+// The lane's column of U into S (issued ahead of the stage's and the block's
+// loads); a lane past n reads nothing and starts from zeros (finite currents).
+template <int M>
+__device__ __forceinline__ void od_prev_load(PFSolverPrev<M>& S, const double* __restrict__ U, int64_t n,
+                                             int64_t e, bool valid) {
+#pragma unroll
+  for (int k = 0; k < M; ++k) {
+    S.ur[k] = valid ? U[(int64_t)(2 * k) * n + e] : 0.0;
+    S.ui[k] = valid ? U[(int64_t)(2 * k + 1) * n + e] : 0.0;
+  }
+}
+
+template <int M>
+__device__ __forceinline__ void od_prev_store(const PFSolverPrev<M>& S, double* __restrict__ U, int64_t n,
+                                              int64_t e, bool valid) {
+  if (!valid) return;
+#pragma unroll
+  for (int k = 0; k < M; ++k) {
+    U[(int64_t)(2 * k) * n + e] = S.ur[k];
+    U[(int64_t)(2 * k + 1) * n + e] = S.ui[k];
+  }
+}
+
+// Iteration 1 (block, powers and the start loaded): od_solve's currents and
+// matvec from the start in S, each element's staged y0' -- u_1 into S, J_1 into
+// the lane's sh.J[1] slots, where iteration 2 expects the previous currents (and
+// the outputs' input when max_iter = 1).  Not tested: min_iter >= 2.
+template <int M>
+__device__ __forceinline__ void od_first_prev(PFSolverPrev<M>& S, const ODStage<M>& g, ODShared<M>& sh) {
+  const int tid = threadIdx.x;
+  double yres[2] = {g.y0r, g.y0i};
+  double A[M], Bs[M], C[M];
+  pf_acc_init<M>(A, C, S.w);
+#pragma unroll
+  for (int i = 0; i < M; ++i) Bs[i] = 0.0;
+  static_for<0, M>([&](auto kk) {
+    constexpr int k = decltype(kk)::value;
+    double ir, ii, y0r, y0i;
+    pf_od_elem<M, k>(y0r, y0i, yres);
+    S.template current_od<k>(y0r, y0i, ir, ii);
+    pf_column<M, k>(A, Bs, C, S.w, ir, ii, ir + ii);
+    sh.J[1][k * kBlock + tid] = make_double2(ir, ii);
+  });
+#pragma unroll
+  for (int i = 0; i < M; ++i) {
+    S.ur[i] = A[i] - Bs[i];
+    S.ui[i] = (C[i] - A[i]) - Bs[i];
+  }
+}
+
+// pgw_pf_prev_reset: the block's direct solution (pf_u0's values) into every
+// env's column of U.
+template <int M>
+__global__ void __launch_bounds__(kBlock) k_pf_prev_reset(const double* __restrict__ block, int64_t n,
+                                                          double* __restrict__ U) {
+  using Lo = PFBlock<M>;
+  const int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  const int l = threadIdx.x & 15;
+  double w[Lo::kPairs], ur[M], ui[M];
+#pragma unroll
+  for (int j = 0; j < Lo::kPairs; ++j) {
+    const int q = 16 * j + l;
+    w[j] = q < Lo::kSize ? block[q] : 0.0;
+  }
+  pf_u0<M>(ur, ui, w);
+  if (e >= n) return;
+#pragma unroll
+  for (int k = 0; k < M; ++k) {
+    U[(int64_t)(2 * k) * n + e] = ur[k];
+    U[(int64_t)(2 * k + 1) * n + e] = ui[k];
+  }
+}
+
+// pgw_pf_solve_prev: k_pf_solve_od_h1's shape -- no response table, no
+// first-iteration table, every env is solved, the output rows' loads issued
+// after the solve.
+template <int M, class IO = double>
+__global__ void __launch_bounds__(kBlock) k_pf_solve_od_prev(PFArgs a, ODArgs o, pgw_pf_tables t, int64_t n,
+                                                             double* __restrict__ U,
+                                                             const IO* __restrict__ ctrl_p,
+                                                             const IO* __restrict__ ctrl_q,
+                                                             IO* __restrict__ v_out,
+                                                             int32_t* __restrict__ iters) {
+  const int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  const bool valid = e < n;
+  __shared__ ODShared<M> sh;
+  ODStage<M> stg;
+  const bool rows_lds = od_rows_lds<M>(a.n_out);     // (uniform)
+  PFSolverPrev<M> S;
+  od_prev_load<M>(S, U, n, e, valid);
+  od_stage_load<M, false>(o, nullptr, stg);
+  S.load(a, t.block);
+  S.pc = (valid && a.n_ctrl > 0 && ctrl_p) ? (double)ctrl_p[e] : 0.0;
+  S.qc = (valid && a.n_ctrl > 0 && ctrl_q) ? (double)ctrl_q[e] : 0.0;
+  od_stage_store<M, false>(o, stg, sh);
+  od_first_prev<M>(S, stg, sh);                      // (reads no staged LDS)
+  __syncthreads();                                   // the staged check rows
+  int it = 0;
+  if (__ballot(valid) != 0ull)                       // (wave-uniform) some env of this wave
+    it = od_solve<M, false, PFSolverPrev<M>>(S, o, stg, valid, sh);
+  double rv[kOdRowQ];
+  if (rows_lds) od_rows_issue<M>(t, a.n_out, rv);
+  od_prev_store<M>(S, U, n, e, valid);               // the newest iterate: the next solve's start
+  double ir[M], ii[M], v0r = 0.0, v0i = 0.0;
+  od_load_J<M>(sh, it, ir, ii);
+  pf_node0<M>(v0r, v0i, S.w, ir, ii);
+  const double m2_0 = fma(v0i, v0i, v0r * v0r);
+  const double v0 = sqrt(m2_0);
+  double vmn = v0, vmx = v0;      // Python min()/max() over the rows in order
+  const double* srow = rows_lds ? od_rows_put<M>(sh, a.n_out, rv) : nullptr;
+  if (v_out || !rows_lds) {
+    pf_rows_out<M>(t, rows_lds, srow, a.n_out, ir, ii, [&](int ro, double v) {
+      if (valid && v_out) v_out[(int64_t)ro * n + e] = (IO)v;
+      vmn = (v < vmn) ? v : vmn;
+      vmx = (v > vmx) ? v : vmx;
+    });
+  } else {
+    // extrema only (as k_pf_solve_od)
+    double mn2 = m2_0, mx2 = mn2;
+    pf_rows_out<M, false>(t, rows_lds, srow, a.n_out, ir, ii, [&](int, double m2) {
+      mn2 = (m2 < mn2) ? m2 : mn2;
+      mx2 = (m2 > mx2) ? m2 : mx2;
+    });
+    vmn = sqrt(mn2);
+    vmx = sqrt(mx2);
+  }
+  if (!valid) return;
+  if (a.n_out > 0) {
+    if (v_out) v_out[e] = (IO)v0;
+    if (t.v_min_out) t.v_min_out[e] = vmn;
+    if (t.v_max_out) t.v_max_out[e] = vmx;
+  }
+  if (iters) iters[e] = it;
+}
+
+// Fused C4 step under snap_start = "previous" (pgw_coord_step_prev):
+// k_pf_solve_od_prev's solve between k_coord_pf_od_h1's prologue (agent powers ->
+// the load of slot 0, 0 + p0 + p1 ... in agent order; Q = 0) and epilogue (the
+// rewards loaded behind the solve, the violation at the coordinated bus, reward =
+// raw + (-share)).  Bit-identical to the agents' kernel, pgw_agent_reduce,
+// pgw_pf_solve_prev and the host's reward transform.
+// on0: bit ag set = agent ag feeds slot 0 (n_ctrl <= 1, so agent_ctrl is 0 or
+// -1 and one word holds CoordPFArgs' agent_ctrl).  agent_power: the buffers'
+// own pointer, as an argument of the prologue's: read from the buffers, one
+// scalar load fetched it together with the epilogue's pointers, and keeping
+// those eight registers across the solve left the kernel a (never accessed)
+// 36-byte scratch frame.
+struct CoordPrevArgs {
+  int32_t n_agents, coordinated, vv_row, on0;
+  double vv_lo, vv_hi, vv_penalty;
+  const void* agent_power;
+};
+template <int M, class Bufs>
+__global__ void __launch_bounds__(kBlock) k_coord_pf_od_prev(CoordPrevArgs c, PFArgs a, ODArgs o, pgw_pf_tables t,
+                                                             int64_t n, double* __restrict__ U, Bufs b) {
+  using Sto = std::remove_pointer_t<decltype(b.reward)>;
+  const int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  const bool valid = e < n;
+  const int64_t ec = valid ? e : 0;
+  __shared__ ODShared<M> sh;
+  ODStage<M> stg;
+  const bool rows_lds = od_rows_lds<M>(a.n_out);     // (uniform) a history slot: every node
+  PFSolverPrev<M> S;
+  od_prev_load<M>(S, U, n, e, valid);
+  od_stage_load<M, false>(o, nullptr, stg);
+  S.load(a, t.block);
+  const Sto* __restrict__ power = static_cast<const Sto*>(c.agent_power);
+  double pc = 0.0;
+#pragma unroll
+  for (int ag = 0; ag < PGW_MAX_AGENTS; ++ag) {
+    const double rp = (double)power[(int64_t)min(ag, c.n_agents - 1) * n + ec] *
+                      ((valid && ag < c.n_agents) ? 1.0 : 0.0);
+    pc = ((c.on0 >> ag) & 1) ? pc + rp : pc;
+  }
+  S.pc = valid ? pc : 0.0;
+  S.qc = 0.0;
+  od_stage_store<M, false>(o, stg, sh);
+  od_first_prev<M>(S, stg, sh);                      // (reads no staged LDS)
+  __syncthreads();                                   // the staged check rows
+  int it = 0;
+  if (__ballot(valid) != 0ull)                       // (wave-uniform) some env of this wave
+    it = od_solve<M, false, PFSolverPrev<M>>(S, o, stg, valid, sh);
+  // the newest iterate, the next step's start: stored first, so that its
+  // registers are free for the row and reward loads
+  od_prev_store<M>(S, U, n, e, valid);
+  double rv[kOdRowQ];
+  if (rows_lds) od_rows_issue<M>(t, a.n_out, rv);
+  Sto rw[PGW_MAX_AGENTS];
+#pragma unroll
+  for (int ag = 0; ag < PGW_MAX_AGENTS; ++ag)
+    rw[ag] = (c.coordinated && ag < c.n_agents) ? b.reward[(int64_t)ag * n + ec] : (Sto)0;
+  double ir[M], ii[M], v0r = 0.0, v0i = 0.0;
+  od_load_J<M>(sh, it, ir, ii);
+  pf_node0<M>(v0r, v0i, S.w, ir, ii);
+  const double v0 = sqrt(fma(v0i, v0i, v0r * v0r));
+  double vsel = v0, vmn = v0, vmx = v0;              // Python min()/max() over the rows in order
+  const double* srow = rows_lds ? od_rows_put<M>(sh, a.n_out, rv) : nullptr;
+  pf_rows_out<M>(t, rows_lds, srow, a.n_out, ir, ii, [&](int ro, double v) {
+    if (valid && b.v_out) b.v_out[(int64_t)ro * n + e] = (Sto)v;
+    vsel = (ro == c.vv_row) ? v : vsel;
+    vmn = (v < vmn) ? v : vmn;
+    vmx = (v > vmx) ? v : vmx;
+  });
+  if (!valid) return;
+  if (b.v_out) b.v_out[e] = (Sto)v0;
+  if (t.v_min_out) t.v_min_out[e] = vmn;
+  if (t.v_max_out) t.v_max_out[e] = vmx;
+  if (b.iters) b.iters[e] = it;
+  if (c.coordinated) {
+    const double vv = pymax(pymax(0.0, c.vv_lo - vsel), vsel - c.vv_hi);
+    if (b.vv) b.vv[e] = (Sto)vv;
+    const double share = (vv * c.vv_penalty) / (double)c.n_agents;
+#pragma unroll
+    for (int ag = 0; ag < PGW_MAX_AGENTS; ++ag)
+      if (ag < c.n_agents) b.reward[(int64_t)ag * n + e] = (Sto)(rw[ag] + (Sto)(-share));
+  }
+}
+
 // Response-table builder (pgw_pf_od_probe): the snap solve at lane e's kW P[e]
 // (Q = 0) in hour e / lanes_per_hour -- that hour's PFArgs (base loads) and
 // first-iteration table -- with the signature of its pieces.
@@ -4364,7 +4599,116 @@ static int32_t coord_step_h1(const pgw_coord_params* p, const pgw_pf_params* pf,
   return check_launch("k_coord_pf_od_h1");
 }
 
+// pgw_pf_prev_reset / pgw_pf_solve_prev / pgw_coord_step_prev (and _f32)
+// The checks of the solve's shape (who: the entry's name).
+static int32_t check_prev(const char* who, const pgw_pf_params* p, const pgw_pf_tables* t, const double* U) {
+  PGW_REQUIRE(t->od, "%s: tables without od (the OpenDSS rule's check rows)", who);
+  const pgw_pf_od* d = t->od;
+  PGW_REQUIRE(p->m == 14 && uniform_band(*p), "%s: needs the fast shape, m = 14 and one voltage band "
+              "(use pgw_pf_solve_general with U_init / U_out)", who);
+  PGW_REQUIRE(p->n_ctrl >= 0 && p->n_ctrl <= 1, "%s: %d controllable slots (at most one)", who, p->n_ctrl);
+  PGW_REQUIRE(!t->U_init && !t->U_out && !t->load_scale, "%s: takes no U_init / U_out / load_scale "
+              "(the state buffer is the U argument)", who);
+  PGW_REQUIRE(!d->resp && !d->resp_v && !d->resp_q && !d->start,
+              "%s: the result depends on the env's history, so it takes no table (od resp / resp_v / resp_q / "
+              "start must be NULL)", who);
+  PGW_REQUIRE(U, "%s: null state buffer U", who);
+  PGW_REQUIRE(p->n_out == 0 || (t->G && t->V0), "%s: missing G/V0", who);
+  PGW_REQUIRE(d->n_rows >= 0 && d->n_rows <= PGW_PF_OD_MAX_ROWS && d->n_rep >= 0 && d->n_rep <= d->n_rows,
+              "%s: od n_rep %d / n_rows %d (<= %d)", who, d->n_rep, d->n_rows, PGW_PF_OD_MAX_ROWS);
+  // (the stage's loads issue unconditionally: one dummy row when n_rows = 0)
+  PGW_REQUIRE(d->rows_V0 && d->rows_G, "%s: od rows missing", who);
+  PGW_REQUIRE(d->min_iter >= 2 && p->max_iter >= 1 && d->tol >= 0.0, "%s: od min_iter / max_iter / tol", who);
+  return PGW_OK;
+}
+
+template <class IO>
+static int32_t pf_solve_prev(const pgw_pf_params* p, const pgw_pf_tables* t, double* U, int64_t n,
+                             const IO* ctrl_p, const IO* ctrl_q, IO* v_out, int32_t* iters, void* stream) {
+  PGW_REQUIRE(p && t && t->block && n >= 0, "pgw_pf_solve_prev: null argument");
+  const int32_t rc = check_prev("pgw_pf_solve_prev", p, t, U);
+  if (rc) return rc;
+  PGW_REQUIRE(p->n_out == 0 || v_out || t->v_min_out || t->v_max_out,
+              "pgw_pf_solve_prev: n_out > 0 but no output (v_out, v_min_out, v_max_out all NULL)");
+  if (n == 0) return PGW_OK;
+  launch_timed(PGW_T_PF_SOLVE, k_pf_solve_od_prev<14, IO>, dim3(grid_for(n)), dim3(kBlock), (hipStream_t)stream,
+               make_pf_args(*p, *t), make_od_args(*t->od, p->max_iter), *t, n, U, ctrl_p, ctrl_q, v_out, iters);
+  return check_launch("k_pf_solve_od_prev");
+}
+
+// The agents' kernel coord_step picks for the layout, then k_coord_pf_od_prev,
+// on one stream.
+template <class Bufs>
+static int32_t coord_step_prev(const pgw_coord_params* p, const pgw_pf_params* pf, const pgw_pf_tables* pft,
+                               double* U, const pgw_coord_step_info* s, int64_t n, const Bufs& b, void* stream) {
+  constexpr bool kF32 = std::is_same<Bufs, pgw_coord_buffers_f32>::value;
+  const char* who = kF32 ? "pgw_coord_step_prev_f32" : "pgw_coord_step_prev";
+  int32_t rc = check_coord(who, p, pf, pft, s, n, b);
+  if (rc) return rc;
+  rc = check_prev(who, pf, pft, U);
+  if (rc) return rc;
+  const bool std_layout = coord_is_std(*p);
+  PGW_REQUIRE(std_layout || !kF32, "%s: needs the standard C4 agent layout (building/pv/storage at 0/6/7)", who);
+  if (n == 0) return PGW_OK;
+  hipStream_t st = (hipStream_t)stream;
+  // a step with a list: the next step's count (k_coord_step_od's job) zeroed here
+  if (b.od_count) {
+    const hipError_t me = hipMemsetAsync(b.od_count + ((b.od_parity & 1) ^ 1), 0, sizeof(int32_t), st);
+    PGW_REQUIRE(me == hipSuccess, "%s: od_count reset: %s", who, hipGetErrorString(me));
+  }
+  const double pv_ob = p->pv.rescale ? (2.0 * std::min(std::max(-s->pv_pmax, p->pv.obs_low), p->pv.obs_high)
+                                        - (p->pv.obs_low + p->pv.obs_high)) / (p->pv.obs_high - p->pv.obs_low)
+                                     : -s->pv_pmax;
+  rc = launch_coord_agents(*p, *s, n, b, pv_ob, std_layout, st);
+  if (rc) return rc;
+  CoordPrevArgs c = {};
+  c.n_agents = p->n_agents;
+  c.coordinated = p->coordinated;
+  c.vv_row = p->vv_row;
+  for (int a = 0; a < p->n_agents; ++a) c.on0 |= (p->agent_ctrl[a] == 0) << a;
+  c.agent_power = b.agent_power;
+  c.vv_lo = p->vv_lo;
+  c.vv_hi = p->vv_hi;
+  c.vv_penalty = p->vv_penalty;
+  launch_timed(PGW_T_COORD_PF, k_coord_pf_od_prev<14, Bufs>, dim3(grid_for(n)), dim3(kBlock), st, c,
+               make_pf_args(*pf, *pft), make_od_args(*pft->od, pf->max_iter), *pft, n, U, b);
+  return check_launch("k_coord_pf_od_prev");
+}
+
 extern "C" {
+
+int32_t pgw_pf_prev_reset(const pgw_pf_params* p, const pgw_pf_tables* t, double* U, int64_t n, void* stream) {
+  PGW_REQUIRE(p && t && t->block && n >= 0, "pgw_pf_prev_reset: null argument");
+  PGW_REQUIRE(p->m == 14, "pgw_pf_prev_reset: needs the fast shape, m = 14 (got %d)", p->m);
+  PGW_REQUIRE(U, "pgw_pf_prev_reset: null state buffer U");
+  if (n == 0) return PGW_OK;
+  hipLaunchKernelGGL(k_pf_prev_reset<14>, dim3(grid_for(n)), dim3(kBlock), 0, (hipStream_t)stream, t->block, n, U);
+  return check_launch("k_pf_prev_reset");
+}
+
+int32_t pgw_pf_solve_prev(const pgw_pf_params* p, const pgw_pf_tables* t, double* U, int64_t n,
+                          const double* ctrl_p, const double* ctrl_q, double* v_out, int32_t* iters,
+                          void* stream) {
+  return pf_solve_prev(p, t, U, n, ctrl_p, ctrl_q, v_out, iters, stream);
+}
+
+int32_t pgw_pf_solve_prev_f32(const pgw_pf_params* p, const pgw_pf_tables* t, double* U, int64_t n,
+                              const float* ctrl_p, const float* ctrl_q, float* v_out, int32_t* iters,
+                              void* stream) {
+  return pf_solve_prev(p, t, U, n, ctrl_p, ctrl_q, v_out, iters, stream);
+}
+
+int32_t pgw_coord_step_prev(const pgw_coord_params* p, const pgw_pf_params* pf, const pgw_pf_tables* pft,
+                            double* U, const pgw_coord_step_info* s, int64_t n, pgw_coord_buffers b,
+                            void* stream) {
+  return coord_step_prev(p, pf, pft, U, s, n, b, stream);
+}
+
+int32_t pgw_coord_step_prev_f32(const pgw_coord_params* p, const pgw_pf_params* pf, const pgw_pf_tables* pft,
+                                double* U, const pgw_coord_step_info* s, int64_t n, pgw_coord_buffers_f32 b,
+                                void* stream) {
+  return coord_step_prev(p, pf, pft, U, s, n, b, stream);
+}
 
 int32_t pgw_pf_solve_h1(const pgw_pf_params* p, const pgw_pf_tables* t, const pgw_pf_h1* h, int64_t n,
                         const double* ctrl_p, const double* ctrl_q, double* v_out, int32_t* iters,

@@ -203,7 +203,8 @@ class OpenDSSSolver(PowerFlowSolver):
                  output_nodes=None, predictor: bool = True, warm_start: bool = False,
                  convergence: str = "opendss", general: bool = None, od_table: bool = True,
                  snap_start: str = "direct", yprim: str = "dss_file", control_loop: str = "host",
-                 multi_bus: str = "general", step_kernel: str = "general", **kwargs):
+                 multi_bus: str = "general", step_kernel: str = "general", start_kernel: str = "general",
+                 **kwargs):
         """convergence: "opendss" (the default) -- OpenDSS's own snap solve as
         the reference runs it (opendss.py:134):
         loads' nominal admittances in Y, start from the direct solution, stop at
@@ -256,8 +257,24 @@ class OpenDSSSolver(PowerFlowSolver):
         torch arithmetic --, and the fused multi-agent step runs it too.
         Anything else (a delta load such as 671, several controllable loads,
         other feeders) falls back to the general kernel; `general` tells which
-        route runs."""
+        route runs.
+        start_kernel (snap_start="previous"; ignored otherwise): "general" (the
+        default) -- the general kernel with U_init / U_out as described above;
+        "fast" -- on a feeder of the fast shape with at most one controllable
+        load (of any number of phase elements), the fast one-lane-per-env
+        kernel (pgw_pf_solve_prev, k_pf_solve_od_prev): each env's element
+        voltages live in a [2 M][N] fp64 state buffer that the kernel reads
+        and overwrites in place; the chain restarts from the direct solution
+        (pgw_pf_prev_reset) at construction and whenever the outputs or the
+        controllable loads change, not at an env's reset(); no response table;
+        the fused multi-agent steps run it too (pgw_coord_step_prev, or
+        pgw_ma_step's agents followed by pgw_pf_solve_prev).  Anything else
+        (several controllable loads, other feeders, RegControls) falls back to
+        the general kernel; `general` tells which route runs."""
         super().__init__(**kwargs)
+        if start_kernel not in ("general", "fast"):
+            raise ValueError("start_kernel must be 'general' or 'fast', got %r" % (start_kernel,))
+        self.start_kernel = start_kernel
         if step_kernel not in ("general", "fast"):
             raise ValueError("step_kernel must be 'general' or 'fast', got %r" % (step_kernel,))
         self.step_kernel = step_kernel
@@ -276,7 +293,9 @@ class OpenDSSSolver(PowerFlowSolver):
                              "the exact fixed point has warm_start=True")
         self.snap_start = snap_start
         if snap_start == "previous":
-            general, od_table = True, False
+            od_table = False
+            if start_kernel != "fast":
+                general = True
         if yprim not in ("dss_file", "step"):
             raise ValueError("yprim must be 'dss_file' or 'step', got %r" % (yprim,))
         if yprim == "step" and (convergence != "opendss" or snap_start != "direct"):
@@ -312,6 +331,9 @@ class OpenDSSSolver(PowerFlowSolver):
         # yprim="step" on the fast kernel (step_kernel="fast"; pgw_pf_solve_h1)
         self._h1_fast = yprim == "step" and self._od_fast
         self._h1f_cache = {}
+        # snap_start="previous" on the fast kernel (start_kernel="fast"; pgw_pf_solve_prev)
+        self._prev_fast = snap_start == "previous" and self._od_fast
+        self._prev_U, self._prev_keepalive = None, None
         if self.feeder.m > _lib.PFG_MAX_M:
             raise ValueError("feeder has %d load phase elements (max %d)" % (self.feeder.m, _lib.PFG_MAX_M))
         if convergence == "opendss":
@@ -430,6 +452,8 @@ class OpenDSSSolver(PowerFlowSolver):
         self._pred_index = {}
         if self._od_fast:
             self._set_od_tables(W, U0, vb_elem)
+        if self._prev_fast:
+            self._prev_restart()
 
     # ------------------------------------------------------------ OpenDSS rule, fast kernels
     OD_MAX_TABLES = 64            # hours of first-iteration tables kept on the device
@@ -1249,7 +1273,12 @@ class OpenDSSSolver(PowerFlowSolver):
         if names != self._ctrl_names:
             self._ctrl_names = names
             self._seen_keys = None
-            if self._h1_fast and not self.h1_fast_serves(names):
+            if self._prev_fast and not self.prev_fast_serves(names):
+                # snap_start="previous": the fast kernel takes one controllable
+                # load; anything else runs the general kernel (U_init / U_out)
+                self._od_fast, self.general, self._prev_fast = False, True, False
+                self.set_output_nodes(self.output_names)
+            elif self._h1_fast and not self.h1_fast_serves(names):
                 # yprim="step": the fast kernel takes one controllable load of
                 # one phase element; anything else runs the general kernel
                 self._od_fast, self.general, self._h1_fast = False, True, False
@@ -1262,6 +1291,40 @@ class OpenDSSSolver(PowerFlowSolver):
                 self.set_output_nodes(self.output_names)
             else:
                 self._base_params()
+                if self._prev_fast:
+                    self._prev_restart()
+
+    def prev_fast_serves(self, names):
+        """snap_start="previous", start_kernel="fast": whether the fast kernel
+        serves these controllable loads -- none, or one load (of any number of
+        phase elements: Y is the DSS file's, there is no per-env correction)."""
+        names = [n for n in names if n in self.load_bus_name]
+        return self._prev_fast and len(names) <= 1
+
+    def _prev_restart(self):
+        """snap_start="previous" on the fast kernel: the chain starts over --
+        every env's column of the state buffer takes the direct solution
+        (pgw_pf_prev_reset), where the general route drops its warm tables."""
+        if self._prev_U is None or tuple(self._prev_U.shape) != (2 * self.M, self.num_envs):
+            self._prev_U = torch.zeros((2 * self.M, self.num_envs), dtype=torch.float64, device=self.device)
+        _lib.check(_lib.lib().pgw_pf_prev_reset(self.params, self.tables, self._prev_U.data_ptr(), self.num_envs,
+                                                _lib.stream_ptr(self.device)))
+
+    def _prev_tables(self):
+        """snap_start="previous" on the fast kernel: the one PFTables of the
+        configuration -- the DSS file's block and rows, od without a
+        first-iteration or response table (the hour enters through step_params
+        only)."""
+        t = self._prev_keepalive
+        if t is None or t._cfg != self._cfg_version:
+            od = _lib.PFOD.from_buffer_copy(self._od_proto)
+            od.start = od.resp = od.resp_v = od.resp_q = None
+            od.resp_v_row = -1
+            t = _lib.PFTables.from_buffer_copy(self.tables)
+            t.od = _lib.C.addressof(od)
+            t._od_ref, t._cfg = od, self._cfg_version     # (the struct lives as long as these tables)
+            self._prev_keepalive = t
+        return t
 
     def h1_fast_serves(self, names):
         """yprim="step", step_kernel="fast": whether the fast kernel serves these
@@ -1440,6 +1503,8 @@ class OpenDSSSolver(PowerFlowSolver):
         episode pays for about one table solve.  Otherwise the cold-start tables."""
         if self._h1_fast:
             return self._h1f_tables(self.hour_of(current_time))
+        if self._prev_fast:
+            return self._prev_tables()
         if self._od_fast:
             return self._od_tables(self.hour_of(current_time))
         if self.general or not (self.use_predictor and len(self._ctrl_names) == 1):
@@ -1555,6 +1620,10 @@ class OpenDSSSolver(PowerFlowSolver):
             _lib.check(_lib.lib().pgw_pf_solve_h1(p, tables, tables._h1, n, _lib.dptr(cp), _lib.dptr(cq),
                                                   _lib.dptr(self.v_out), _lib.dptr(self._iters),
                                                   _lib.stream_ptr(self.device)))
+        elif self._prev_fast:
+            _lib.check(_lib.lib().pgw_pf_solve_prev(p, tables, self._prev_U.data_ptr(), n, _lib.dptr(cp),
+                                                    _lib.dptr(cq), _lib.dptr(self.v_out), _lib.dptr(self._iters),
+                                                    _lib.stream_ptr(self.device)))
         else:
             _lib.check(fn(p, tables, n, _lib.dptr(cp), _lib.dptr(cq), _lib.dptr(self.v_out),
                           _lib.dptr(self._iters), _lib.stream_ptr(self.device)))

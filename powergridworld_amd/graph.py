@@ -322,7 +322,7 @@ class StepGraph:
 
 class CoordStepGraph:
     """Captured steps of the fused multi-agent step (MultiAgentEnv fused path,
-    pgw_coord_step / _f32 / _general / _h1): `steps` consecutive steps per graph,
+    pgw_coord_step / _f32 / _general / _h1 / _prev): `steps` consecutive steps per graph,
     captured once per episode position (and step parity of the fused step's
     list counters) on first use, each step's launches holding that step's
     constants as the eager step builds them (_step_entry: exogenous rows, PV
@@ -400,6 +400,8 @@ class CoordStepGraph:
             for (info, pfp, pft, _), b in launches:
                 if F["h1"]:           # yprim="step": the hour's pgw_pf_h1 with its tables
                     _lib.check(fn(F["params"], pfp, pft, pft._h1, info, n, b, st))
+                elif F["prev"]:       # snap_start="previous": every step reads and writes the state buffer
+                    _lib.check(fn(F["params"], pfp, pft, solver._prev_U.data_ptr(), info, n, b, st))
                 else:
                     _lib.check(fn(F["params"], pfp, pft, info, n, b, st))
         g = _capture(env.device, launch)

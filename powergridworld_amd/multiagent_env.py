@@ -482,7 +482,10 @@ class MultiAgentEnv(Env):
             return "the general power flow (large feeder or convergence='opendss') has no fp32 fused step"
         if getattr(self.pf_solver, "regulators", None) is not None:
             return "RegControl (the control loop runs in OpenDSSSolver.calculate_power_flow)"
-        if getattr(self.pf_solver, "snap_start", "direct") != "direct":
+        if getattr(self.pf_solver, "snap_start", "direct") != "direct" and \
+                not self.pf_solver.prev_fast_serves(sorted(set(self.agent_name_bus_map.values()))):
+            # start_kernel="fast" with the agents on one load takes
+            # pgw_coord_step_prev (the agents' kernel, then k_coord_pf_od_prev)
             return "snap_start='previous' (each env's solve starts from its own previous solution)"
         if getattr(self.pf_solver, "yprim", "dss_file") != "dss_file" and \
                 not self.pf_solver.h1_fast_serves(sorted(set(self.agent_name_bus_map.values()))):
@@ -601,6 +604,12 @@ class MultiAgentEnv(Env):
             raise RuntimeError("voltages of an earlier step: the fused path solves the other nodes "
                                "on demand from the step's agent powers, which a later step overwrote")
         F, solver = self._fused, self.pf_solver
+        if getattr(solver, "_prev_fast", False):
+            # the step's solve started from the env's previous solution and has
+            # overwritten it with its own: no second solver can restate the step
+            raise RuntimeError("snap_start='previous', start_kernel='fast': the fused step keeps only the rows it "
+                               "writes (each env's start was overwritten by its own solve); construct the env "
+                               "with record_history=True, whose steps write every node")
         full = self.__dict__.get("_pf_full")
         if full is None:
             cfg = dict(self.pf_config["config"], warm_start=False)
@@ -727,6 +736,12 @@ class MultiAgentEnv(Env):
         F["h1"] = bool(getattr(self.pf_solver, "_h1_fast", False))
         if F["h1"]:
             F["kernel"] = "pgw_coord_step_h1_f32" if f32 else "pgw_coord_step_h1"
+        # snap_start="previous" on the fast kernel: the entries that also take
+        # the solver's per-env state buffer (read per launch: a restart of the
+        # chain may re-allocate it)
+        F["prev"] = bool(getattr(self.pf_solver, "_prev_fast", False))
+        if F["prev"]:
+            F["kernel"] = "pgw_coord_step_prev_f32" if f32 else "pgw_coord_step_prev"
         obs = F["obs"]
         bufs.obs = F["Mat"](obs.data_ptr(), 1, obs.stride(1))
         bufs.obs_stride_agent = obs.stride(0)
@@ -761,6 +776,8 @@ class MultiAgentEnv(Env):
         self._obs_rows_forget()
         self._fused = F
         assert not (F["h1"] and self._one_launch_ok()), "the H1 step has no response table"
+        assert not (F["prev"] and self._one_launch_ok()), \
+            "the snap_start='previous' step has no response table: the result depends on each env's history"
         if self._one_launch_ok():
             self.set_pf_list(True)
 
@@ -796,7 +813,10 @@ class MultiAgentEnv(Env):
                 return "RegControl (the control loop runs in OpenDSSSolver.calculate_power_flow)"
             if self.dtype != torch.float64:
                 return "RegControl on the fused multi-agent step is fp64 only"
-        if getattr(self.pf_solver, "snap_start", "direct") != "direct":
+        if getattr(self.pf_solver, "snap_start", "direct") != "direct" and \
+                not self.pf_solver.prev_fast_serves(sorted(set(self.agent_name_bus_map.values()))):
+            # start_kernel="fast" with the agents on one load: pgw_ma_step's
+            # agents, then pgw_pf_solve_prev on the bus loads
             return "snap_start='previous' (each env's solve starts from its own previous solution)"
         if getattr(self.pf_solver, "yprim", "dss_file") != "dss_file" and \
                 not self.pf_solver.h1_fast_serves(sorted(set(self.agent_name_bus_map.values()))):
@@ -919,6 +939,8 @@ class MultiAgentEnv(Env):
                     "general": _lib.lib().pgw_pf_solve_general if solver.general else None,
                     # yprim="step" on the fast kernel: pgw_pf_solve_h1 after the agents' step
                     "h1": _lib.lib().pgw_pf_solve_h1 if getattr(solver, "_h1_fast", False) else None,
+                    # snap_start="previous" on the fast kernel: pgw_pf_solve_prev after the agents' step
+                    "prev": _lib.lib().pgw_pf_solve_prev if getattr(solver, "_prev_fast", False) else None,
                     # RegControls (control_loop="device"): the solver's own launch of
                     # pgw_pf_solve_regulated in place of the general power flow
                     "regloop": solver.regulators is not None}
@@ -967,6 +989,10 @@ class MultiAgentEnv(Env):
             rc = M["fn"](args, None, None, self.num_envs, None, None, st) or \
                 M["h1"](pfp, pft, pft._h1, self.num_envs, M["bus_p"].data_ptr() if args.n_bus else None, None,
                         v_out, M["iters"].data_ptr(), st)
+        elif M["prev"] is not None:   # the agents' step, then the solve from and into the env's state buffer
+            rc = M["fn"](args, None, None, self.num_envs, None, None, st) or \
+                M["prev"](pfp, pft, solver._prev_U.data_ptr(), self.num_envs,
+                          M["bus_p"].data_ptr() if args.n_bus else None, None, v_out, M["iters"].data_ptr(), st)
         elif M["general"] is None:
             rc = M["fn"](args, pfp, pft, self.num_envs, v_out, M["iters"].data_ptr(), st)
         else:     # the agents' step, then the general power flow on its bus loads
@@ -1135,6 +1161,8 @@ class MultiAgentEnv(Env):
         fn = getattr(_lib.lib(), F["kernel"])
         if F["h1"]:
             rc = fn(F["params"], pfp, pft, pft._h1, info, self.num_envs, bufs, st)
+        elif F["prev"]:
+            rc = fn(F["params"], pfp, pft, solver._prev_U.data_ptr(), info, self.num_envs, bufs, st)
         else:
             rc = fn(F["params"], pfp, pft, info, self.num_envs, bufs, st)
         if rc:

@@ -19,7 +19,11 @@ the general kernel (step_kernel="general", the default) / the fused multi-agent
 step and the fast kernel (step_kernel="fast", pgw_pf_solve_h1); C4YG / C4YF:
 the coordinated 5-building scenario (C4) at 65 536 envs under yprim="step",
 step_kernel="fast", on the generic path (fused=False) / on the fused step
-(pgw_coord_step_h1); C3F / C3G8F:
+(pgw_coord_step_h1); HETPG / HETPF and C4PG / C4PF: the heterogeneous scenario
+and C4 at 65 536 envs under snap_start="previous" (every env's solve continues
+from its previous solution), start_kernel="general" (the default: the general
+kernel, the generic paths) / "fast" (the fused steps with pgw_pf_solve_prev /
+pgw_coord_step_prev); C3F / C3G8F:
 C3 with fp32 storage (pgw_mc_agent_step_f32); C3L: C3 at
 65 536 envs; C2Gk / C3Gk: the step replayed from captured hipGraphs of k steps,
 C3 through the device clocks; C3Pk / HSPk: captured once per episode position,
@@ -158,7 +162,7 @@ def bench_c3(dev, steps, warmup, n=16384, pool=16, graph=0, clocked=True, dtype=
 
 
 def bench_het(dev, steps, warmup, n=65536, pool=16, fused="auto", conv="opendss", table=True, vrec=True, qrec=True,
-              rrows=True, dtype=torch.float64, multi_bus=None, step_kernel=None):
+              rrows=True, dtype=torch.float64, multi_bus=None, step_kernel=None, start_kernel=None):
     from powergridworld_amd.scenarios.heterogeneous import make_env_config
     from powergridworld_amd.multiagent_env import MultiAgentEnv
     cfg = make_env_config(pf_convergence=conv)
@@ -169,6 +173,9 @@ def bench_het(dev, steps, warmup, n=65536, pool=16, fused="auto", conv="opendss"
         table = False
     if step_kernel:                # yprim="step": no response table, every env is solved
         cfg["pf_config"]["config"].update(yprim="step", step_kernel=step_kernel)
+        table = False
+    if start_kernel:               # snap_start="previous": the result depends on history, no table
+        cfg["pf_config"]["config"].update(snap_start="previous", start_kernel=start_kernel)
         table = False
     env = MultiAgentEnv(**cfg, num_envs=n, device=dev, fused=fused, dtype=dtype)
     env.pf_solver.od_table = table
@@ -202,6 +209,8 @@ def bench_het(dev, steps, warmup, n=65536, pool=16, fused="auto", conv="opendss"
         name = "HETM" + multi_bus[0].upper()
     if step_kernel:
         name = "HETY" + step_kernel[0].upper()
+    if start_kernel:
+        name = "HETP" + start_kernel[0].upper()
     return dict(config=name,
                 workload="3-agent heterogeneous (MC building, grid-aware PV farm, EV 25x40)"
                          + (" on buses %s" % ", ".join(MULTI_BUSES) if multi_bus else "") + " + IEEE-13 PF, "
@@ -245,6 +254,42 @@ def bench_c4y(dev, steps, warmup, n=65536, pool=16, fused=True):
                 workload="coordinated 5-building (C4) + IEEE-13 PF under yprim='step', "
                          + ("fused step (%s)" % env._fused["kernel"] if fused else "generic path"),
                 pf_kernel="general" if env.pf_solver.general else "fast", pf_yprim=env.pf_solver.yprim,
+                batch=n, agents=na, steps=steps, seconds=dt)
+
+
+def bench_c4p(dev, steps, warmup, n=65536, pool=16, start_kernel="fast"):
+    """C4 under snap_start="previous": start_kernel="general" runs the generic
+    path on the general kernel (both fused steps refuse the route), "fast" the
+    fused step (pgw_coord_step_prev); packed actions on the fused path, the same
+    draws as dicts on the generic one."""
+    from powergridworld_amd.scenarios.coordinated import CoordinatedMultiBuildingControlEnv, make_c4_config
+    cfg = make_c4_config()
+    cfg["pf_config"]["config"].update(snap_start="previous", start_kernel=start_kernel)
+    env = CoordinatedMultiBuildingControlEnv(**cfg, num_envs=n, device=dev)
+    fused = start_kernel == "fast"
+    assert (env._fused is not None) == fused and env.pf_solver._prev_fast == fused
+    gen = torch.Generator(dev).manual_seed(0)
+    na, dims = len(env.agents), [c.action_space.shape[0] for c in env.agents[0].envs]
+    packed = [torch.empty((na, n, sum(dims)), dtype=torch.float64, device=dev).uniform_(-1, 1, generator=gen)
+              for _ in range(pool)]
+    if fused:
+        acts = packed
+    else:
+        offs = [sum(dims[:i]) for i in range(len(dims))]
+        acts = [{a.name: {c.name: p[ai, :, o:o + d] for c, o, d in zip(a.envs, offs, dims)}
+                 for ai, a in enumerate(env.agents)} for p in packed]
+    k = [0]
+
+    def step():
+        _, _, dones, _ = env.step(acts[k[0] % pool])
+        k[0] += 1
+        return dones["__all__"]
+
+    dt = timed_loop(env, step, env.reset, steps, warmup)
+    return dict(config="C4PF" if fused else "C4PG",
+                workload="coordinated 5-building (C4) + IEEE-13 PF under snap_start='previous', "
+                         + ("fused step (%s)" % env._fused["kernel"] if fused else "generic path"),
+                pf_kernel="general" if env.pf_solver.general else "fast", pf_snap_start=env.pf_solver.snap_start,
                 batch=n, agents=na, steps=steps, seconds=dt)
 
 
@@ -305,6 +350,10 @@ def main():
            "HETYG": lambda *a: bench_het(*a, step_kernel="general"),
            "HETYF": lambda *a: bench_het(*a, step_kernel="fast"),
            "C4YG": lambda *a: bench_c4y(*a, fused=False), "C4YF": lambda *a: bench_c4y(*a, fused=True),
+           "HETPG": lambda *a: bench_het(*a, start_kernel="general"),
+           "HETPF": lambda *a: bench_het(*a, start_kernel="fast"),
+           "C4PG": lambda *a: bench_c4p(*a, start_kernel="general"),
+           "C4PF": lambda *a: bench_c4p(*a, start_kernel="fast"),
            "C2G1": lambda *a: bench_c2(*a, graph=1), "C2G8": lambda *a: bench_c2(*a, graph=8),
            "C3G1": lambda *a: bench_c3(*a, graph=1), "C3G8": lambda *a: bench_c3(*a, graph=8),
            "C3P1": lambda *a: bench_c3(*a, graph=1, clocked=False),
