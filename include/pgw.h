@@ -1051,6 +1051,45 @@ int32_t pgw_coord_step_rows(const pgw_coord_params* p, const pgw_pf_params* pf,
                             const pgw_pf_tables* pft, const pgw_coord_step_info* s, int64_t n,
                             pgw_coord_buffers b, void* stream, uint32_t obs_rows_held);
 
+/* Episode reset of every agent of the standard C4 layout in one launch
+ * (k_coord_reset, one lane per (agent, env)): what pgw_building_reset (with no
+ * external observation inputs), pgw_pv_obs, pgw_battery_reset and the zero
+ * fills of the storage's and the agent's real power do per agent: the same
+ * operations in the same order (the standard building's input selections as
+ * constants, each observation's division as the IEEE quotient formed from a
+ * host reciprocal), so the same bits.
+ *   init          initial state of charge, agent a's n values at
+ *                 init + a * init_stride_agent
+ *   sampled_init  as pgw_battery_params.sampled_init (which this entry ignores):
+ *                 non-zero = a drawn SoC, stored as it is; 0 = a given one,
+ *                 clipped to [soc_min, soc_max]
+ *   p_consumed, reward_state, storage_power   per agent, [n] each, each
+ *                 nullable: the building's p_consumed (:= 0) and reward_state
+ *                 (:= the reward of the reset state), the storage's real
+ *                 power (:= 0) */
+typedef struct pgw_coord_reset_args {
+  const double* init;
+  int64_t init_stride_agent;
+  int32_t sampled_init, pad_;
+  double* p_consumed[PGW_MAX_AGENTS];
+  double* reward_state[PGW_MAX_AGENTS];
+  double* storage_power[PGW_MAX_AGENTS];
+} pgw_coord_reset_args;
+
+/* ex0: the building's exogenous row 0; pv_pmax0: the PV's data[0].  Of b it
+ * uses obs / obs_stride_agent (rows 0-14 the building's, 15 the PV's, 16 the
+ * storage's; nontemporal stores), x (updated in place: x_k carries over), soc
+ * and agent_power (:= 0); b.reward and the PV's real power are not touched, as
+ * the component resets leave them.  PGW_ERR_ARG before any launch for a null
+ * p / ex0 / r / r->init / b.obs.ptr / b.x / b.soc / b.agent_power, n < 0,
+ * n_agents outside 1..PGW_MAX_AGENTS, a layout other than the standard one
+ * (building / pv / storage at observations 0 / 15 / 16, the default 15
+ * building observations), a grid-aware PV, and a building that observes
+ * bus_voltage, min_voltage, max_voltage or p_setpoint.  n == 0: PGW_OK, no
+ * launch. */
+int32_t pgw_coord_reset(const pgw_coord_params* p, const pgw_building_exo* ex0, double pv_pmax0,
+                        int64_t n, pgw_coord_buffers b, const pgw_coord_reset_args* r, void* stream);
+
 /* fp32-storage variant: every per-env buffer fp32, arithmetic in fp64 (the
  * power flow included: the agent powers are widened and summed in fp64, the
  * solve is the fp64 one).  Standard C4 agent layout only ([building, pv,

@@ -216,6 +216,12 @@ class CoordStepInfo(C.Structure):
     _fields_ = [("ex_t", BuildingExo), ("ex_next", BuildingExo), ("pv_pmax", f64)]
 
 
+class CoordResetArgs(C.Structure):
+    _fields_ = [("init", vp), ("init_stride_agent", i64), ("sampled_init", i32), ("pad_", i32),
+                ("p_consumed", vp * MAX_AGENTS), ("reward_state", vp * MAX_AGENTS),
+                ("storage_power", vp * MAX_AGENTS)]
+
+
 HS_MAX_VEHICLES, HS_MAX_DEV = 64, 4
 
 
@@ -389,6 +395,7 @@ _SIGS = {
                              CoordBuffers, vp]),
     "pgw_coord_step_rows": (i32, [P(CoordParams), P(PFParams), P(PFTables), P(CoordStepInfo), i64,
                                   CoordBuffers, vp, C.c_uint32]),
+    "pgw_coord_reset": (i32, [P(CoordParams), P(BuildingExo), f64, i64, CoordBuffers, P(CoordResetArgs), vp]),
     "pgw_coord_step_f32": (i32, [P(CoordParams), P(PFParams), P(PFTables), P(CoordStepInfo), i64,
                                  CoordBuffersF32, vp]),
     "pgw_coord_step_general": (i32, [P(CoordParams), P(PFGParams), P(PFGTables), P(CoordStepInfo), i64,

@@ -42,7 +42,8 @@ import torch
 # caches, host-table keep-alives and the voltage mappings (views of buffers saved
 # under their own names; MultiAgentEnv.load_state_dict re-arms them)
 _SKIP_NAMES = ("version", "_ver", "cache", "_lib", "_memo", "keepalive", "voltages")
-_SKIP_EXACT = ("history", "_hist", "_bv")  # the history lists and their device ring (emptied on load)
+_SKIP_EXACT = ("history", "_hist", "_bv",  # the history lists and their device ring (emptied on load)
+               "_fused_reset")             # reset()'s switch, counter and the scratch its draws pass through
 # the power-flow solver's per-hour tables (first-iteration / response / node
 # records, predictor): derived data whose host-side index (_od_index,
 # _pred_index) is not state -- a restore keeps the live tables and their index

@@ -1061,6 +1061,109 @@ static bool coord_is_std(const pgw_coord_params& p) {
   return true;
 }
 
+// Episode reset of the standard C4 agents, one lane per (agent, env):
+// k_building_reset (no external observation inputs), the PV's observation,
+// k_battery_reset and the zero fills of MultiComponentEnv.reset and
+// EnergyStorageEnv.reset (pgw_coord_reset; per agent it replaces 16 launches).
+// The building is the standard one (coord_is_std), so its input selections
+// are compile-time indices and the observations are scaled by host
+// reciprocals, as in std_agent_compute: k_building_reset's operations one for
+// one (clip_fast == clip, exact_div == the IEEE quotient), in a tenth of the
+// instructions.  With the generic device functions (building_state_update,
+// building_write_obs: selections and divisions per lane) the kernel was bound
+// by instruction issue, 36-42 us at C4 for 86.5 MB
+// (profiles/r18/coord_reset_resource_usage.txt).
+// The per-agent pointers are picked with constant indices (a dynamic index
+// into a by-value argument is the private-copy hazard of PGW_KERNARG0's note).
+static_assert(sizeof(pgw_coord_reset_args) == 24 + 3 * 8 * PGW_MAX_AGENTS,
+              "pgw_coord_reset_args: the binding's layout (it is not in pgw_struct_sizes)");
+__global__ void __launch_bounds__(kBlock) k_coord_reset(pgw_coord_params p_, pgw_building_exo ex0,
+                                                        double pmax0, int64_t n, pgw_coord_buffers b,
+                                                        pgw_coord_reset_args r, StdDerived dv) {
+  const pgw_coord_params& p = PGW_KERNARG0(pgw_coord_params);   // (no private copy)
+  const int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  const int a = blockIdx.y;
+  if (e >= n) return;
+  double* xp = b.x + (int64_t)a * 5 * n + e;
+  double xs[5], T[5];
+#pragma unroll
+  for (int z = 0; z < 5; ++z) xs[z] = xp[z * n];
+  const double init = r.init[(int64_t)a * r.init_stride_agent + e];
+  double *pcons = nullptr, *rstate = nullptr, *bat_rp = nullptr;
+#pragma unroll
+  for (int k = 0; k < PGW_MAX_AGENTS; ++k) {
+    pcons = a == k ? r.p_consumed[k] : pcons;
+    rstate = a == k ? r.reward_state[k] : rstate;
+    bat_rp = a == k ? r.storage_power[k] : bat_rp;
+  }
+  // ---- building (k_building_reset)
+  const pgw_building_params& B = p.bld;
+#pragma unroll
+  for (int z = 0; z < 5; ++z) T[z] = B.T_init[z];
+  // two filter updates with the same u (five_zone_rom_env.py:160-173); u is
+  // building_state_update's reset form (u_pos[7] = q_cool) under the standard
+  // selections, bld_std_step's u0..u3
+#pragma unroll
+  for (int it = 0; it < 2; ++it) {
+#pragma unroll
+    for (int z = 0; z < 5; ++z) {
+      const int nz = z < 2 ? 4 : (z == 2 ? 3 : 2);
+      const double u0 = ex0.T_oa - T[z];
+      const double u1 = ex0.q_cool[z];
+      const double u2 = T[nz] - T[z];
+      const double u3 = ex0.q_solar[z];
+      double bu = B.B[z][0] * u0;
+      bu = bu + B.B[z][1] * u1;
+      bu = bu + B.B[z][2] * u2;
+      bu = bu + B.B[z][3] * u3;
+      xs[z] = B.A[z] * xs[z] + bu;
+    }
+#pragma unroll
+    for (int z = 0; z < 5; ++z) {
+      double yhat = B.C[z] * xs[z];
+      double yact = T[z] - B.mean[z];
+      xs[z] = xs[z] + B.K[z] * (yact - yhat);
+    }
+  }
+#pragma unroll
+  for (int z = 0; z < 5; ++z) {
+    xp[z * n] = xs[z];
+    T[z] = B.C[z] * xs[z] + B.mean[z];               // temp_dynamics (dynamics.py:75-85)
+  }
+  if (pcons) pcons[e] = 0.0;
+  if (rstate) rstate[e] = building_reward(B, T, ex0.comfort_lb, ex0.comfort_ub, 0.0);
+  double* op = b.obs.ptr + a * b.obs_stride_agent + e * b.obs.s_env;
+  // building_write_obs for obs_var = 5 + j and p_consumed = 0 (the rescale test
+  // hoisted out of the loop: bld_std_step's note)
+  const double lb = ex0.comfort_lb, ub = ex0.comfort_ub;
+  auto obs_value = [&](int j) {
+    return j < 5 ? T[j] - ub : j < 10 ? lb - T[j - 5] : j == 10 ? lb
+         : j == 11 ? ub : j == 12 ? ex0.T_oa : j == 13 ? 0.0 : ex0.time_of_day;
+  };
+  if (B.rescale) {
+#pragma unroll
+    for (int j = 0; j < 15; ++j) {
+      const double c = clip_fast(obs_value(j), B.obs_low[j], B.obs_high[j]);
+      st_obs(op + j * b.obs.s_dim, exact_div(2.0 * c - dv.obs_sum[j], dv.obs_rng[j], dv.obs_rcp[j]));
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < 15; ++j)
+      st_obs(op + j * b.obs.s_dim, clip_fast(obs_value(j), B.obs_low[j], B.obs_high[j]));
+  }
+  // ---- pv (PVEnv.get_obs at index 0; its real power stays)
+  st_obs(op + 15 * b.obs.s_dim, pv_obs(p.pv, pmax0));
+  // ---- storage (k_battery_reset, EnergyStorageEnv.reset's zero fill)
+  const double s = r.sampled_init ? init : clip(init, p.bat.soc_min, p.bat.soc_max);
+  b.soc[(int64_t)a * n + e] = s;
+  const double sc = clip_fast(s, p.bat.soc_min, p.bat.soc_max);
+  st_obs(op + 16 * b.obs.s_dim,
+         p.bat.rescale ? exact_div(2.0 * sc - dv.bat_sum, dv.bat_rng, dv.bat_rcp) : s);
+  if (bat_rp) bat_rp[e] = 0.0;
+  // ---- MultiComponentEnv.reset's zero fill
+  b.agent_power[(int64_t)a * n + e] = 0.0;
+}
+
 // K2: one lane per env -- bus loads (multiagent_env.py:171-181), power flow
 // (opendss.py:80-135), CoordinatedMultiBuildingControlEnv.reward_transform
 // (train.py:51-63, 71-88) applied to the agent rewards in place.
@@ -4755,6 +4858,25 @@ int32_t pgw_coord_step_rows(const pgw_coord_params* p, const pgw_pf_params* pf, 
                             const pgw_coord_step_info* s, int64_t n, pgw_coord_buffers b, void* stream,
                             uint32_t obs_rows_held) {
   return coord_step(p, pf, pft, s, n, b, stream, obs_rows_held);
+}
+
+int32_t pgw_coord_reset(const pgw_coord_params* p, const pgw_building_exo* ex0, double pv_pmax0,
+                        int64_t n, pgw_coord_buffers b, const pgw_coord_reset_args* r, void* stream) {
+  PGW_REQUIRE(p && ex0 && r && r->init && b.obs.ptr && b.x && b.soc && b.agent_power && n >= 0,
+              "pgw_coord_reset: null argument");
+  PGW_REQUIRE(p->n_agents >= 1 && p->n_agents <= PGW_MAX_AGENTS, "pgw_coord_reset: n_agents %d outside 1..%d",
+              p->n_agents, PGW_MAX_AGENTS);
+  PGW_REQUIRE(p->bld.n_obs >= 0 && p->bld.n_obs <= PGW_BLD_MAX_OBS, "pgw_coord_reset: bad n_obs");
+  for (int j = 0; j < p->bld.n_obs; ++j)
+    PGW_REQUIRE(p->bld.obs_var[j] < PGW_BV_BUS_VOLTAGE || p->bld.obs_var[j] > PGW_BV_P_SETPOINT,
+                "pgw_coord_reset: the building observes bus_voltage, min_voltage, max_voltage or p_setpoint");
+  PGW_REQUIRE(!p->pv.grid_aware, "pgw_coord_reset: grid-aware PV");
+  PGW_REQUIRE(coord_is_std(*p),
+              "pgw_coord_reset: needs the standard C4 agent layout (building/pv/storage at observations 0/15/16)");
+  if (n == 0) return PGW_OK;
+  hipLaunchKernelGGL(k_coord_reset, dim3(grid_for(n), p->n_agents), dim3(kBlock), 0, (hipStream_t)stream, *p,
+                     *ex0, pv_pmax0, n, b, *r, make_std_derived(*p));
+  return check_launch("k_coord_reset");
 }
 
 int32_t pgw_coord_step_f32(const pgw_coord_params* p, const pgw_pf_params* pf,
