@@ -1127,6 +1127,48 @@ int32_t pgw_coord_step_f32(const pgw_coord_params* p, const pgw_pf_params* pf,
                            const pgw_pf_tables* pft, const pgw_coord_step_info* s, int64_t n,
                            pgw_coord_buffers_f32 b, void* stream);
 
+/* pgw_coord_reset for the fp32-storage step (k_coord_reset_f32, one launch, one
+ * lane per (agent, env)), under the f32 entries' rounding contract: x_k is read
+ * from b.x as fp32 and widened, the arithmetic is pgw_coord_reset's operation
+ * for operation in fp64, and every value is rounded once, at its fp32 store.
+ * The same unrounded fp64 values go to the components' own fp64 buffers, so
+ * that whoever reads a component (an attribute, a checkpoint, a narrowing copy
+ * back into the step's buffers) reads what the component entries would have
+ * left there; the observations and the reward state are formed from the
+ * unrounded state, never from a value after its fp32 store.  The result is
+ * bit for bit pgw_coord_reset on the widened x_k, each fp32 output rounded
+ * once.
+ *   init, init_stride_agent, sampled_init   as pgw_coord_reset_args' (fp64)
+ *   x              per agent, [5][n]: the building's state
+ *   p_consumed, reward_state, storage_power   as pgw_coord_reset_args'
+ *   soc            per agent, [n]: the storage's state of charge
+ *   bld_obs, pv_obs, bat_obs   per agent: the components' observation buffers
+ *                  ([n x 15], [n x 1], [n x 1]; nontemporal stores)
+ * Every per-agent pointer (a pgw_mat's ptr) is nullable: null skips that store. */
+typedef struct pgw_coord_reset_args_f32 {
+  const double* init;
+  int64_t init_stride_agent;
+  int32_t sampled_init, pad_;
+  double* x[PGW_MAX_AGENTS];
+  double* p_consumed[PGW_MAX_AGENTS];
+  double* reward_state[PGW_MAX_AGENTS];
+  double* soc[PGW_MAX_AGENTS];
+  double* storage_power[PGW_MAX_AGENTS];
+  pgw_mat bld_obs[PGW_MAX_AGENTS];
+  pgw_mat pv_obs[PGW_MAX_AGENTS];
+  pgw_mat bat_obs[PGW_MAX_AGENTS];
+} pgw_coord_reset_args_f32;
+
+/* Of b it uses obs / obs_stride_agent (rows 0-16, nontemporal stores), x
+ * (updated in place), soc, agent_power (:= 0) and reward (:= 0: the fp32 env
+ * zeroes the step's reward rows at a reset, where pgw_coord_reset leaves
+ * b.reward alone); the PV's real power and the actions are not touched.
+ * PGW_ERR_ARG before any launch for everything pgw_coord_reset refuses and for
+ * a null b.reward.  n == 0: PGW_OK, no launch. */
+int32_t pgw_coord_reset_f32(const pgw_coord_params* p, const pgw_building_exo* ex0, double pv_pmax0,
+                            int64_t n, pgw_coord_buffers_f32 b, const pgw_coord_reset_args_f32* r,
+                            void* stream);
+
 /* The coordinated step under OpenDSSSolver yprim="step" (H1, pgw_pf_solve_h1's
  * map): two launches on the stream, the agents' kernel pgw_coord_step picks for
  * the layout (fp64: the standard C4 layout or any other; fp32: the standard one

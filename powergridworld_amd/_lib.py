@@ -222,6 +222,15 @@ class CoordResetArgs(C.Structure):
                 ("storage_power", vp * MAX_AGENTS)]
 
 
+class CoordResetArgsF32(C.Structure):
+    """pgw_coord_reset_args_f32: the draws (fp64) and, per agent, the components'
+    own fp64 buffers (each nullable)."""
+    _fields_ = [("init", vp), ("init_stride_agent", i64), ("sampled_init", i32), ("pad_", i32),
+                ("x", vp * MAX_AGENTS), ("p_consumed", vp * MAX_AGENTS), ("reward_state", vp * MAX_AGENTS),
+                ("soc", vp * MAX_AGENTS), ("storage_power", vp * MAX_AGENTS),
+                ("bld_obs", Mat * MAX_AGENTS), ("pv_obs", Mat * MAX_AGENTS), ("bat_obs", Mat * MAX_AGENTS)]
+
+
 HS_MAX_VEHICLES, HS_MAX_DEV = 64, 4
 
 
@@ -398,6 +407,8 @@ _SIGS = {
     "pgw_coord_reset": (i32, [P(CoordParams), P(BuildingExo), f64, i64, CoordBuffers, P(CoordResetArgs), vp]),
     "pgw_coord_step_f32": (i32, [P(CoordParams), P(PFParams), P(PFTables), P(CoordStepInfo), i64,
                                  CoordBuffersF32, vp]),
+    "pgw_coord_reset_f32": (i32, [P(CoordParams), P(BuildingExo), f64, i64, CoordBuffersF32,
+                                  P(CoordResetArgsF32), vp]),
     "pgw_coord_step_general": (i32, [P(CoordParams), P(PFGParams), P(PFGTables), P(CoordStepInfo), i64,
                                      CoordBuffers, vp]),
     "pgw_coord_step_h1": (i32, [P(CoordParams), P(PFParams), P(PFTables), P(PFH1), P(CoordStepInfo), i64,

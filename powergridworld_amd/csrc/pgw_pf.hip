@@ -1164,6 +1164,121 @@ __global__ void __launch_bounds__(kBlock) k_coord_reset(pgw_coord_params p_, pgw
   b.agent_power[(int64_t)a * n + e] = 0.0;
 }
 
+// k_coord_reset for the fp32-storage step (pgw_coord_reset_f32): x_k widened
+// on load, k_coord_reset's arithmetic operation for operation in fp64, every
+// value rounded once at its fp32 store into the step's buffers, and the same
+// unrounded value stored as fp64 into the component's own buffer where the
+// caller gave one (what the components' fp64 resets leave there).  The
+// observations and the reward state come from the unrounded state.  A twin,
+// not a template of k_coord_reset: that kernel's text, and so its code, stays.
+// 336 B per lane (28 read, 100 + 208 written).
+static_assert(sizeof(pgw_coord_reset_args_f32) == 24 + (5 * 8 + 3 * sizeof(pgw_mat)) * PGW_MAX_AGENTS,
+              "pgw_coord_reset_args_f32: the binding's layout (it is not in pgw_struct_sizes)");
+__global__ void __launch_bounds__(kBlock) k_coord_reset_f32(pgw_coord_params p_, pgw_building_exo ex0,
+                                                            double pmax0, int64_t n, pgw_coord_buffers_f32 b,
+                                                            pgw_coord_reset_args_f32 r, StdDerived dv) {
+  const pgw_coord_params& p = PGW_KERNARG0(pgw_coord_params);   // (no private copy)
+  const int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  const int a = blockIdx.y;
+  if (e >= n) return;
+  float* xp = b.x + (int64_t)a * 5 * n + e;
+  double xs[5], T[5];
+#pragma unroll
+  for (int z = 0; z < 5; ++z) xs[z] = (double)xp[z * n];
+  const double init = r.init[(int64_t)a * r.init_stride_agent + e];
+  // the agent's component-side buffers, picked with constant indices
+  double *cx = nullptr, *pcons = nullptr, *rstate = nullptr, *csoc = nullptr, *bat_rp = nullptr;
+  pgw_mat ob = {nullptr, 0, 0}, opv = {nullptr, 0, 0}, obt = {nullptr, 0, 0};
+#pragma unroll
+  for (int k = 0; k < PGW_MAX_AGENTS; ++k) {
+    cx = a == k ? r.x[k] : cx;
+    pcons = a == k ? r.p_consumed[k] : pcons;
+    rstate = a == k ? r.reward_state[k] : rstate;
+    csoc = a == k ? r.soc[k] : csoc;
+    bat_rp = a == k ? r.storage_power[k] : bat_rp;
+    ob.ptr = a == k ? r.bld_obs[k].ptr : ob.ptr;
+    ob.s_env = a == k ? r.bld_obs[k].s_env : ob.s_env;
+    ob.s_dim = a == k ? r.bld_obs[k].s_dim : ob.s_dim;
+    opv.ptr = a == k ? r.pv_obs[k].ptr : opv.ptr;
+    opv.s_env = a == k ? r.pv_obs[k].s_env : opv.s_env;
+    obt.ptr = a == k ? r.bat_obs[k].ptr : obt.ptr;
+    obt.s_env = a == k ? r.bat_obs[k].s_env : obt.s_env;
+  }
+  // ---- building (k_coord_reset's, on the widened x_k)
+  const pgw_building_params& B = p.bld;
+#pragma unroll
+  for (int z = 0; z < 5; ++z) T[z] = B.T_init[z];
+#pragma unroll
+  for (int it = 0; it < 2; ++it) {
+#pragma unroll
+    for (int z = 0; z < 5; ++z) {
+      const int nz = z < 2 ? 4 : (z == 2 ? 3 : 2);
+      const double u0 = ex0.T_oa - T[z];
+      const double u1 = ex0.q_cool[z];
+      const double u2 = T[nz] - T[z];
+      const double u3 = ex0.q_solar[z];
+      double bu = B.B[z][0] * u0;
+      bu = bu + B.B[z][1] * u1;
+      bu = bu + B.B[z][2] * u2;
+      bu = bu + B.B[z][3] * u3;
+      xs[z] = B.A[z] * xs[z] + bu;
+    }
+#pragma unroll
+    for (int z = 0; z < 5; ++z) {
+      double yhat = B.C[z] * xs[z];
+      double yact = T[z] - B.mean[z];
+      xs[z] = xs[z] + B.K[z] * (yact - yhat);
+    }
+  }
+#pragma unroll
+  for (int z = 0; z < 5; ++z) {
+    xp[z * n] = (float)xs[z];
+    if (cx) cx[z * n + e] = xs[z];
+    T[z] = B.C[z] * xs[z] + B.mean[z];               // (from the unrounded state)
+  }
+  if (pcons) pcons[e] = 0.0;
+  if (rstate) rstate[e] = building_reward(B, T, ex0.comfort_lb, ex0.comfort_ub, 0.0);
+  float* op = b.obs.ptr + a * b.obs_stride_agent + e * b.obs.s_env;
+  double* cop = ob.ptr ? ob.ptr + e * ob.s_env : nullptr;
+  const double lb = ex0.comfort_lb, ub = ex0.comfort_ub;
+  auto obs_value = [&](int j) {
+    return j < 5 ? T[j] - ub : j < 10 ? lb - T[j - 5] : j == 10 ? lb
+         : j == 11 ? ub : j == 12 ? ex0.T_oa : j == 13 ? 0.0 : ex0.time_of_day;
+  };
+  if (B.rescale) {
+#pragma unroll
+    for (int j = 0; j < 15; ++j) {
+      const double c = clip_fast(obs_value(j), B.obs_low[j], B.obs_high[j]);
+      const double v = exact_div(2.0 * c - dv.obs_sum[j], dv.obs_rng[j], dv.obs_rcp[j]);
+      st_obs(op + j * b.obs.s_dim, v);
+      if (cop) st_obs(cop + j * ob.s_dim, v);
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < 15; ++j) {
+      const double v = clip_fast(obs_value(j), B.obs_low[j], B.obs_high[j]);
+      st_obs(op + j * b.obs.s_dim, v);
+      if (cop) st_obs(cop + j * ob.s_dim, v);
+    }
+  }
+  // ---- pv
+  const double vpv = pv_obs(p.pv, pmax0);
+  st_obs(op + 15 * b.obs.s_dim, vpv);
+  if (opv.ptr) st_obs(opv.ptr + e * opv.s_env, vpv);
+  // ---- storage
+  const double s = r.sampled_init ? init : clip(init, p.bat.soc_min, p.bat.soc_max);
+  b.soc[(int64_t)a * n + e] = (float)s;
+  if (csoc) csoc[e] = s;
+  const double sc = clip_fast(s, p.bat.soc_min, p.bat.soc_max);
+  const double vbat = p.bat.rescale ? exact_div(2.0 * sc - dv.bat_sum, dv.bat_rng, dv.bat_rcp) : s;
+  st_obs(op + 16 * b.obs.s_dim, vbat);
+  if (obt.ptr) st_obs(obt.ptr + e * obt.s_env, vbat);
+  if (bat_rp) bat_rp[e] = 0.0;
+  // ---- MultiComponentEnv.reset's zero fill, and the fp32 env's of the step's reward rows
+  b.agent_power[(int64_t)a * n + e] = 0.0f;
+  b.reward[(int64_t)a * n + e] = 0.0f;
+}
+
 // K2: one lane per env -- bus loads (multiagent_env.py:171-181), power flow
 // (opendss.py:80-135), CoordinatedMultiBuildingControlEnv.reward_transform
 // (train.py:51-63, 71-88) applied to the agent rewards in place.
@@ -4877,6 +4992,26 @@ int32_t pgw_coord_reset(const pgw_coord_params* p, const pgw_building_exo* ex0, 
   hipLaunchKernelGGL(k_coord_reset, dim3(grid_for(n), p->n_agents), dim3(kBlock), 0, (hipStream_t)stream, *p,
                      *ex0, pv_pmax0, n, b, *r, make_std_derived(*p));
   return check_launch("k_coord_reset");
+}
+
+int32_t pgw_coord_reset_f32(const pgw_coord_params* p, const pgw_building_exo* ex0, double pv_pmax0,
+                            int64_t n, pgw_coord_buffers_f32 b, const pgw_coord_reset_args_f32* r,
+                            void* stream) {
+  PGW_REQUIRE(p && ex0 && r && r->init && b.obs.ptr && b.x && b.soc && b.agent_power && b.reward && n >= 0,
+              "pgw_coord_reset_f32: null argument");
+  PGW_REQUIRE(p->n_agents >= 1 && p->n_agents <= PGW_MAX_AGENTS,
+              "pgw_coord_reset_f32: n_agents %d outside 1..%d", p->n_agents, PGW_MAX_AGENTS);
+  PGW_REQUIRE(p->bld.n_obs >= 0 && p->bld.n_obs <= PGW_BLD_MAX_OBS, "pgw_coord_reset_f32: bad n_obs");
+  for (int j = 0; j < p->bld.n_obs; ++j)
+    PGW_REQUIRE(p->bld.obs_var[j] < PGW_BV_BUS_VOLTAGE || p->bld.obs_var[j] > PGW_BV_P_SETPOINT,
+                "pgw_coord_reset_f32: the building observes bus_voltage, min_voltage, max_voltage or p_setpoint");
+  PGW_REQUIRE(!p->pv.grid_aware, "pgw_coord_reset_f32: grid-aware PV");
+  PGW_REQUIRE(coord_is_std(*p), "pgw_coord_reset_f32: needs the standard C4 agent layout "
+                                "(building/pv/storage at observations 0/15/16)");
+  if (n == 0) return PGW_OK;
+  hipLaunchKernelGGL(k_coord_reset_f32, dim3(grid_for(n), p->n_agents), dim3(kBlock), 0, (hipStream_t)stream,
+                     *p, *ex0, pv_pmax0, n, b, *r, make_std_derived(*p));
+  return check_launch("k_coord_reset_f32");
 }
 
 int32_t pgw_coord_step_f32(const pgw_coord_params* p, const pgw_pf_params* pf,

@@ -138,10 +138,11 @@ class MultiAgentEnv(Env):
         # neither the switch nor the counter nor the held key is checkpointed state.
         self._obs_rows = {"on": bool(obs_row_skip) and os.environ.get("PGW_OBS_ROW_SKIP", "1") != "0",
                           "skipped": 0, "key": None}
-        # fused fp64 env: reset() resets every agent in one launch (pgw_coord_reset;
-        # see reset()).  PGW_FUSED_RESET=0 turns it off for every env built while
-        # it is set (A/B runs).  Switch, counter and the draws' scratch tensor sit
-        # in a dict the checkpoint skips: none of them is state.
+        # fused C4 env: reset() resets every agent in one launch (pgw_coord_reset,
+        # fp32 storage: pgw_coord_reset_f32; see reset()).  PGW_FUSED_RESET=0 turns
+        # it off for every env built while it is set (A/B runs).  Switch, counter
+        # and the draws' scratch tensor sit in a dict the checkpoint skips: none of
+        # them is state.
         self._fused_reset = {"on": bool(fused_reset) and os.environ.get("PGW_FUSED_RESET", "1") != "0",
                              "resets": 0, "u": None, "why": None, "checked": False}
         self.rescale_spaces = rescale_spaces
@@ -304,18 +305,20 @@ class MultiAgentEnv(Env):
 
     @property
     def fused_resets(self):
-        """Resets that took the one-launch route (pgw_coord_reset) so far."""
+        """Resets that took the one-launch route (pgw_coord_reset, fp32 storage:
+        pgw_coord_reset_f32) so far."""
         return self._fused_reset["resets"]
 
     def _fused_reset_ok(self):
-        """reset() may take the one-launch route: the fp64 fused step of the
-        standard C4 agent, and agents whose resets pgw_coord_reset restates
-        (fused_reset_why; looked at once, the classes and tables do not change)."""
+        """reset() may take the one-launch route: the fused step of the standard
+        C4 agent (fp64 or fp32 storage), and agents whose resets pgw_coord_reset
+        restates (fused_reset_why; looked at once, the classes and tables do not
+        change)."""
         R = self._fused_reset
         if not R["checked"]:
             R["checked"] = True
-            if self._fused is None or self.dtype != torch.float64:
-                R["why"] = "not the fp64 fused step"
+            if self._fused is None or self.dtype not in (torch.float64, torch.float32):
+                R["why"] = "not the fused C4 step"
             elif self._f32_fusable() is not None or not self._std_layout(self._fused["params"]):
                 R["why"] = "not the standard C4 agent layout"
             else:
@@ -331,8 +334,8 @@ class MultiAgentEnv(Env):
         element-wise operations run once over all agents' draws, operation for
         operation: the same bits.  False (nothing done): a buffer is not where
         the fused step put it, and the per-component resets run instead."""
-        F, R = self._fused, self._fused_reset
-        n, na = self.num_envs, len(self.agents)
+        F = self._fused
+        n = self.num_envs
         step_b = F["bufs"]
         power0 = self.agents[0]._real_power
         for ai, agent in enumerate(self.agents):
@@ -345,18 +348,7 @@ class MultiAgentEnv(Env):
                     any(t.dtype != torch.float64 or not t.is_contiguous() or t.shape != (n,)
                         for t in (agent._real_power, bld.p_consumed, bld._reward_state, bat._real_power)):
                 return False
-        U = R["u"]
-        if U is None:
-            U = R["u"] = torch.empty((na, n), dtype=torch.float64, device=self.device)
-        bat0 = self.agents[0].envs[2]
-        for ai, agent in enumerate(self.agents):
-            torch.rand(n, generator=agent.envs[2]._gen, out=U[ai])
-        # EnergyStorageEnv._sample_initial_storage on all agents' draws
-        lo = 0.5 * (1.0 + math.erf(-1.0 / math.sqrt(2.0)))
-        hi = 0.5 * (1.0 + math.erf(1.0 / math.sqrt(2.0)))
-        U.mul_(hi - lo).add_(lo).mul_(2.0).sub_(1.0)
-        torch.special.erfinv(U, out=U)
-        U.mul_(math.sqrt(2.0)).mul_(bat0.initial_storage_std).add_(bat0.initial_storage_mean)
+        U = self._reset_draws()
         b = _lib.CoordBuffers()
         b.obs, b.obs_stride_agent = step_b.obs, step_b.obs_stride_agent
         b.x, b.soc = step_b.x, step_b.soc
@@ -371,7 +363,81 @@ class MultiAgentEnv(Env):
         bld0, pv0 = self.agents[0].envs[0], self.agents[0].envs[1]
         _lib.check(_lib.lib().pgw_coord_reset(F["params"], bld0._exo[0], float(pv0.data[0]), n, b, r,
                                               _lib.stream_ptr(self.device)))
-        # the host side of the resets not called
+        self._reset_fused_host()
+        return True
+
+    def _reset_fused_f32(self):
+        """_reset_fused for fp32 storage (pgw_coord_reset_f32): the same fp64
+        draws; the launch reads x_k from the step's fp32 buffer, rounds every
+        value once into the step's buffers and stores the same unrounded fp64
+        values into the components' own buffers -- what _f32_sync(up=True), the
+        components' fp64 resets and _f32_sync(up=False) leave, bit for bit,
+        without either copy pass.  False (nothing done): a buffer is not what
+        the fused setup made it, and that route runs instead."""
+        F = self._fused
+        n = self.num_envs
+        step_b = F["bufs"]
+        power0 = self.agents[0]._real_power
+        f64, f32 = torch.float64, torch.float32
+        for k, shape in (("obs", (len(self.agents), 17, n)), ("x", (len(self.agents), 5, n)),
+                         ("soc", (len(self.agents), n)), ("reward", (len(self.agents), n))):
+            if F[k].dtype != f32 or F[k].shape != shape or not F[k].is_contiguous():
+                return False
+        if step_b.obs.ptr != F["obs"].data_ptr() or step_b.x != F["x"].data_ptr() or \
+                step_b.soc != F["soc"].data_ptr() or step_b.reward != F["reward"].data_ptr():
+            return False
+        for ai, agent in enumerate(self.agents):
+            bld, pv, bat = agent.envs
+            if agent._real_power.data_ptr() != power0.data_ptr() + 4 * n * ai or \
+                    agent._real_power.dtype != f32 or agent._real_power.shape != (n,) or \
+                    bld.x.dtype != f64 or bld.x.shape != (5, n) or not bld.x.is_contiguous() or \
+                    any(t.dtype != f64 or not t.is_contiguous() or t.shape != (n,)
+                        for t in (bat.soc, bld.p_consumed, bld._reward_state, bat._real_power)) or \
+                    any(e._obs.dtype != f64 or e._obs.shape != (n, d)
+                        for e, d in ((bld, 15), (pv, 1), (bat, 1))):
+                return False
+        U = self._reset_draws()
+        b = _lib.CoordBuffersF32()
+        b.obs, b.obs_stride_agent = step_b.obs, step_b.obs_stride_agent
+        b.x, b.soc, b.reward = step_b.x, step_b.soc, step_b.reward
+        b.agent_power = power0.data_ptr()      # (read now: the history ring re-points the agents' power)
+        r = _lib.CoordResetArgsF32()
+        r.init, r.init_stride_agent, r.sampled_init = U.data_ptr(), U.stride(0), 1
+        for ai, agent in enumerate(self.agents):
+            bld, pv, bat = agent.envs
+            r.x[ai], r.soc[ai] = bld.x.data_ptr(), bat.soc.data_ptr()
+            r.p_consumed[ai] = bld.p_consumed.data_ptr()
+            r.reward_state[ai] = bld._reward_state.data_ptr()
+            r.storage_power[ai] = bat._real_power.data_ptr()
+            r.bld_obs[ai], r.pv_obs[ai], r.bat_obs[ai] = _lib.mat(bld._obs), _lib.mat(pv._obs), _lib.mat(bat._obs)
+        bld0, pv0 = self.agents[0].envs[0], self.agents[0].envs[1]
+        _lib.check(_lib.lib().pgw_coord_reset_f32(F["params"], bld0._exo[0], float(pv0.data[0]), n, b, r,
+                                                  _lib.stream_ptr(self.device)))
+        self._reset_fused_host()
+        return True
+
+    def _reset_draws(self):
+        """The initial states of charge of all agents, [n_agents, n] fp64: the
+        components' own draws and _sample_initial_storage's operations."""
+        R = self._fused_reset
+        n, na = self.num_envs, len(self.agents)
+        U = R["u"]
+        if U is None:
+            U = R["u"] = torch.empty((na, n), dtype=torch.float64, device=self.device)
+        bat0 = self.agents[0].envs[2]
+        for ai, agent in enumerate(self.agents):
+            torch.rand(n, generator=agent.envs[2]._gen, out=U[ai])
+        # EnergyStorageEnv._sample_initial_storage on all agents' draws
+        lo = 0.5 * (1.0 + math.erf(-1.0 / math.sqrt(2.0)))
+        hi = 0.5 * (1.0 + math.erf(1.0 / math.sqrt(2.0)))
+        U.mul_(hi - lo).add_(lo).mul_(2.0).sub_(1.0)
+        torch.special.erfinv(U, out=U)
+        U.mul_(math.sqrt(2.0)).mul_(bat0.initial_storage_std).add_(bat0.initial_storage_mean)
+        return U
+
+    def _reset_fused_host(self):
+        """After the one-launch reset: the host side of the resets not called."""
+        R = self._fused_reset
         for agent in self.agents:
             bld, pv, bat = agent.envs
             bld.time_index, bld._prev_viol_reward = 0, None
@@ -381,11 +447,11 @@ class MultiAgentEnv(Env):
             agent._ep_step = 0
         oob_poll(self.oob_count)
         R["resets"] += 1
-        return True
 
     def reset(self) -> Dict[str, any]:
-        """multiagent_env.py:125-140.  Fused fp64 path, standard C4 agents: one
-        launch resets all agents (pgw_coord_reset) unless ``fused_reset=False``,
+        """multiagent_env.py:125-140.  Fused path, standard C4 agents: one launch
+        resets all agents (pgw_coord_reset; with fp32 storage pgw_coord_reset_f32,
+        which also stands in for both of _f32_sync's passes) unless ``fused_reset=False``,
         a component class or an agent overrides ``reset``, ``get_obs`` or
         ``_sample_initial_storage``, the storages differ in
         ``initial_storage_mean`` / ``_std`` or the buildings in their first
@@ -411,12 +477,15 @@ class MultiAgentEnv(Env):
             self.voltages = self.pf_solver.bus_voltages = _FusedVoltages(
                 self, self.pf_solver.bus_voltages, self._fused_steps, reset=True)
         f32 = self._fused is not None and self.dtype != torch.float64
-        if f32:
-            self._f32_sync(up=True)
-        if self._fused_reset_ok() and self._reset_fused():
+        if self._fused_reset_ok() and (self._reset_fused_f32() if f32 else self._reset_fused()):
             self._prewarm_steps()
+            if f32:
+                self._f32_voltages()
+                return self._fused["obs_dict"]
             # get_obs()'s dict of the components' observation views, no launch
             return {agent.name: {e.name: e._obs for e in agent.envs} for agent in self.agents}
+        if f32:
+            self._f32_sync(up=True)
         for agent in self.agents:
             kwargs = self.get_external_obs_vars(agent)
             _ = agent.reset(**kwargs)
@@ -722,10 +791,16 @@ class MultiAgentEnv(Env):
                 F["reward"][ai].zero_()
                 F["agent_power"][ai].zero_()
         if not up:
-            F["v_out"][: self.pf_solver.v_out.shape[0]].copy_(self.pf_solver.v_out)
-            self.voltages = F["voltages"]
-            if len(self.pf_solver.output_names) < self.pf_solver.feeder.n:
-                self.voltages = _FusedVoltages(self, F["voltages"], self._fused_steps, reset=True)
+            self._f32_voltages()
+
+    def _f32_voltages(self):
+        """fp32 fused path, after a reset: the reset solve's voltage rows into the
+        step's fp32 rows, and env.voltages on them."""
+        F = self._fused
+        F["v_out"][: self.pf_solver.v_out.shape[0]].copy_(self.pf_solver.v_out)
+        self.voltages = F["voltages"]
+        if len(self.pf_solver.output_names) < self.pf_solver.feeder.n:
+            self.voltages = _FusedVoltages(self, F["voltages"], self._fused_steps, reset=True)
 
     def _full_voltages(self, step_no, reset=False):
         """Every node's voltage for the fused step `step_no` (_FusedVoltages): the

@@ -12,7 +12,9 @@ every reset between two TIMED steps this prints
   - the number of kernels (and copies, when a memory_copy_trace.csv is given
     too) dispatched in that gap,
   - the sum of their durations,
-and k_coord_reset's own duration where the gap holds one.
+and k_coord_reset's own duration where the gap holds one.  A trace of the
+fp32 loop (tools/gpu/ab_reset_f32.py --child, the same step sequence) reads
+the same way: the names match k_coord_step_od_f32 and k_coord_reset_f32 too.
 
 usage: python tools/gpu/reset_gap.py kernel_trace.csv [memory_copy_trace.csv]
                                      [--steps 572] [--warmup 30] [--names]
